@@ -11,11 +11,14 @@ A "step" is one full pass enc -> unet -> dec over one batch of synthetic latents
 replayed as one HIP graph.  Batch-sharded data parallel inference has no data-path collective:
 every rank denoises its own batch of 4, scaling is "weak", value = N * K / max-over-ranks(time).
 
-Rank 0 additionally reports
+A plain run sets up, warms up, times the K steps and prints the JSON line (``ms_per_step`` = milliseconds per timed
+step).  ``--dump-outputs DIR`` also writes the last timed step's outputs as DIR/<name>.npy (float32; same arguments =>
+same inputs, so two builds can be compared output for output).  ``--full`` adds, on rank 0,
   roofline     -- the dominant kernel class of the step, measured live with HIP events around every launch of one
                   eager step (events recorded on the launch stream): algorithmic FLOP (or bytes) / summed duration
+  loop         -- the 50-step sampling loops of the pipeline and their parity against the committed oracle loop
   cpu_baseline -- the CPU fp32 oracle (oracle/unirenderer_oracle.py, "port") timed on this host's cores on one
-                  step of the same shape.
+                  step of the same shape, and the parity of the timed step's outputs against it.
 """
 import argparse
 import json
@@ -149,6 +152,28 @@ def make_inputs(B, L, dev, dtype, seed):
     return x_t, cond, ehs, t_img, t_attr
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, outputs):
+    """Write ``outputs`` ({name: tensor}) as ``path/<name>.npy`` in float32.  Above 64 MiB in all, every array is replaced
+    by the same fraction of its elements, drawn by a fixed seed (the same elements on every run of the same shapes)."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    total = sum(t.numel() for t in outputs.values()) * 4
+    keep = min(1.0, DUMP_LIMIT_BYTES / total)
+    for name, t in sorted(outputs.items()):
+        a = t.detach().float().reshape(-1)
+        if keep < 1.0:
+            g = torch.Generator(device=a.device).manual_seed(0)
+            idx = torch.randperm(a.numel(), device=a.device, generator=g)[: int(a.numel() * keep)].sort().values
+            a = a[idx]
+        else:
+            a = a.view(t.shape)
+        np.save(os.path.join(path, f"{name}.npy"), a.cpu().numpy())
+
+
 def measure_roofline(step_fn, by_shape=False, live_traffic=False, extra_args=()):
     """One eager step (same executor as the timed mode, launched serially on one stream) with every launch
     bracketed by HIP events on the launch stream; per kernel class sums."""
@@ -258,8 +283,7 @@ def measure_traffic_live(klass, extra_args, steps=2, timeout=150):
         for counter in ("FETCH_SIZE", "WRITE_SIZE"):
             out = os.path.join(tmp, counter)
             cmd = ["rocprofv3", "--pmc", counter, "--kernel-trace", "-d", out, "-o", "p", "--output-format", "csv", "--",
-                   sys.executable, os.path.join(ROOT, "bench.py"), "--steps", str(steps), "--warmup", "1", "--no-cpu-baseline",
-                   "--no-roofline", "--no-loop"] + list(extra_args)
+                   sys.executable, os.path.join(ROOT, "bench.py"), "--steps", str(steps), "--warmup", "1"] + list(extra_args)
             proc = subprocess.Popen(cmd, cwd=ROOT, env=env, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, start_new_session=True)
             try:
                 rc = proc.wait(timeout=timeout)
@@ -498,6 +522,11 @@ def main():
     ap.add_argument("--dtype", default="fp16", choices=["fp16", "bf16"])
     ap.add_argument("--direction", default="inverse", choices=["inverse", "render"],
                     help="inverse: enc+unet+dec (headline, cfg 3/5); render: enc+unet only (cfg 2)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the last timed step's outputs to DIR/<name>.npy (float32, at most 64 MiB in all)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the roofline, the sampling loops and the CPU baseline, with their parity checks "
+                         "(the --no-* options below leave out single legs of a --full run)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-loop", action="store_true", help="skip the 50-step sampling-loop timings (the `loop` object)")
     ap.add_argument("--no-roofline", action="store_true")
@@ -510,6 +539,10 @@ def main():
     ap.add_argument("--kernel-table", action="store_true", help="print the per-kernel-class table to stderr")
     ap.add_argument("--shape-table", default="", help="write a per-(kernel, problem shape) table (JSON) to this path")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if (args.kernel_table or args.shape_table) and not args.full:
+        ap.error("--kernel-table / --shape-table come from the roofline leg: add --full")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -534,7 +567,7 @@ def main():
     from uni_renderer_amd.graph import GraphedDualStreamStep, dual_stream_step
 
     _lib.load()  # no HIP library -> fail loudly
-    want_cpu = rank == 0 and world == 1 and not args.no_cpu_baseline
+    want_cpu = args.full and rank == 0 and world == 1 and not args.no_cpu_baseline
     fp32_state = [] if want_cpu else None
     models = build_models(dev, dtype, fp32_state=fp32_state)
     inputs = make_inputs(args.batch, args.latent, dev, dtype, seed=100 + rank)
@@ -543,14 +576,18 @@ def main():
                                    concurrent=not args.no_concurrent, mode=args.mode)
     runner.load_inputs(*inputs)
     if args.eager:
+        eager_out = {}
+
         def one():
             with torch.no_grad():
-                dual_stream_step(*models, runner.x_t, runner.cond, runner.ehs, runner.t_img, runner.t_attr,
-                                 run_decoder=(args.direction == "inverse"))
+                eager_out.update(dual_stream_step(*models, runner.x_t, runner.cond, runner.ehs, runner.t_img, runner.t_attr,
+                                                  run_decoder=(args.direction == "inverse")))
         one()
+        last_outputs = lambda: eager_out
     else:
         runner.capture()
         one = runner.replay
+        last_outputs = lambda: runner.out
 
     def barrier():
         if dist_on:
@@ -570,6 +607,8 @@ def main():
         t = torch.tensor([dt], device=dev, dtype=torch.float64)
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         dt = float(t.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last_outputs())
 
     if rank == 0:
         out = {
@@ -602,7 +641,7 @@ def main():
                                     if os.environ.get("UR_PRECISE_RESIDUAL", "1") != "0" else "plain (UR_PRECISE_RESIDUAL=0)"),
             },
         }
-        if not args.no_roofline:  # rank 0 only (this block), at every N: the kernels are the same on every rank
+        if args.full and not args.no_roofline:  # rank 0 only (this block), at every N: the kernels are the same on every rank
             side, runner.side = runner.side, None  # serial launches for per-kernel timing
             # HBM traffic of the dominant kernel: measured live (one GPU, headline-style run) by two PMC child runs of the
             # same workload; the committed profile is the fallback
@@ -624,7 +663,7 @@ def main():
                     json.dump(stable, f)
         profiled = (any(k.startswith(("ROCPROF", "ROCPROFILER", "ROCP_")) for k in os.environ)
                     or "rocprofiler" in os.environ.get("LD_PRELOAD", ""))  # a counter pass over 400 more graph replays takes minutes
-        if world == 1 and not args.no_loop and not args.eager and not profiled:
+        if args.full and world == 1 and not args.no_loop and not args.eager and not profiled:
             try:
                 out["loop"] = sampling_loops(models, args.batch, args.latent, dev, dtype)
             except Exception as e:  # the headline line must not depend on this leg

@@ -109,13 +109,13 @@ def test_bench_runs_with_the_drivers_command_line_and_spawns_its_own_ranks():
 
 
 def test_bench_line_carries_the_contract_fields_with_a_live_roofline():
-    """One default-style run (roofline on, live PMC traffic attempted, CPU baseline off for time) at a small configuration:
+    """One --full run (roofline on, live PMC traffic attempted, CPU baseline off for time) at a small configuration:
     the JSON line has every field of the bench contract, and the roofline object is self-consistent."""
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", TMPDIR="/tmp")
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
         env.pop(k, None)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--batch", "2",
-           "--latent", "32"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "3", "--warmup", "1", "--no-cpu-baseline",
+           "--batch", "2", "--latent", "32"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=1200, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
@@ -130,6 +130,31 @@ def test_bench_line_carries_the_contract_fields_with_a_live_roofline():
     assert roof["bound"] in ("hbm", "mfma") and abs(roof["frac"] - roof["achieved"] / roof["peak"]) < 1e-3
     if roof["traffic"] is not None:
         assert roof["traffic"] > 0 and roof["traffic_source"].startswith(("LIVE", "STATIC"))
+
+
+def test_plain_bench_run_times_only_and_dumps_the_last_steps_outputs(tmp_path):
+    """A plain run (no --full) prints the headline line without the --full legs, and --dump-outputs writes the last timed
+    step's outputs as float32 .npy files: the same arrays on a second run with the same arguments."""
+    import numpy as np
+
+    env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
+        env.pop(k, None)
+    got = []
+    for run in ("a", "b"):
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "4", "--warmup", "1", "--batch", "2", "--latent", "16",
+               "--dump-outputs", str(tmp_path / run)]
+        r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-3000:]
+        line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+        assert line["steps"] == 4 and line["ms_per_step"] > 0
+        assert not {"roofline", "loop", "cpu_baseline", "kernel_classes"} & set(line)
+        got.append({n: np.load(tmp_path / run / f"{n}.npy") for n in ("img_pred", "attr_pred")})
+    assert sorted(os.listdir(tmp_path / "a")) == ["attr_pred.npy", "img_pred.npy"]
+    for n, shape in (("img_pred", (2, 4, 16, 16)), ("attr_pred", (2, 28, 16, 16))):
+        a, b = got[0][n], got[1][n]
+        assert a.dtype == np.float32 and a.shape == shape and np.isfinite(a).all() and np.abs(a).max() > 0
+        assert np.array_equal(a, b), n
 
 
 GRAPH_WORKER = r'''

@@ -7,10 +7,10 @@ OUT=$R/gpurun_out/prof_$TAG
 RAW=/tmp/ur_raw_$TAG   # raw traces / counter dumps are tens of MB: never under gpurun_out/ (64 MiB copy-back limit)
 mkdir -p $OUT $RAW
 cd $R
-timeout 600 python bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err
-python bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-loop --no-live-traffic --shape-table $OUT/per_shape_eager_events.json > /dev/null 2>&1
+timeout 600 python bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err
+python bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --no-loop --no-live-traffic --shape-table $OUT/per_shape_eager_events.json > /dev/null 2>&1
 export TMPDIR=/tmp
-(cd $R && timeout 420 rocprofv3 --kernel-trace --stats -d $RAW/stats -o $TAG --output-format csv -- python bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-loop --no-live-traffic > $OUT/bench_under_rocprofv3.json 2> $OUT/rocprof_stats.err)
+(cd $R && timeout 420 rocprofv3 --kernel-trace --stats -d $RAW/stats -o $TAG --output-format csv -- python bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --no-loop --no-live-traffic > $OUT/bench_under_rocprofv3.json 2> $OUT/rocprof_stats.err)
 (cd $R && timeout 420 rocprofv3 --pmc FETCH_SIZE --kernel-trace -d $RAW/pmc_fetch -o p --output-format csv -- python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-loop --no-live-traffic > /dev/null 2>&1)
 (cd $R && timeout 420 rocprofv3 --pmc WRITE_SIZE --kernel-trace -d $RAW/pmc_write -o p --output-format csv -- python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-loop --no-live-traffic > /dev/null 2>&1)
 (cd $R && timeout 420 rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_BUSY_CYCLES SQ_WAVE_CYCLES --kernel-trace -d $RAW/pmc_mfma -o p --output-format csv -- python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-loop --no-live-traffic > /dev/null 2>&1)

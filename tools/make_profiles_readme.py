@@ -158,16 +158,16 @@ of `optim.FusedAdamW`), `{tag}_vae_bench.json` (`tools/vae_bench.py`); round 2's
 
 | file | what |
 |---|---|
-| `{tag}_bench_default.json` | `python bench.py` (defaults: 30 steps, 5 warm-up, fp16, B=4, 64x64 latent), un-profiled: the headline line incl. `roofline` and `cpu_baseline` |
-| `{tag}_kernel_stats.csv` | `rocprofv3 --kernel-trace --stats -- python bench.py --steps 10 --warmup 2 --no-cpu-baseline` (16 step executions in the process: 2 capture warm-ups, 2+10 graph replays, 2 eager roofline steps) |
+| `{tag}_bench_default.json` | `python bench.py --full` (defaults: 30 steps, 5 warm-up, fp16, B=4, 64x64 latent), un-profiled: the headline line incl. `roofline` and `cpu_baseline` |
+| `{tag}_kernel_stats.csv` | `rocprofv3 --kernel-trace --stats -- python bench.py --full --steps 10 --warmup 2 --no-cpu-baseline` (16 step executions in the process: 2 capture warm-ups, 2+10 graph replays, 2 eager roofline steps) |
 | `{tag}_bench_under_rocprofv3.json` | the bench line printed by that profiled run |
-| `{tag}_per_shape_eager_events.json` | per (kernel class, problem shape) table of one eager step, each launch bracketed by HIP events on the launch stream (`bench.py --shape-table`); eager launches of small kernels include launch latency |
+| `{tag}_per_shape_eager_events.json` | per (kernel class, problem shape) table of one eager step, each launch bracketed by HIP events on the launch stream (`bench.py --full --shape-table`); eager launches of small kernels include launch latency |
 | `pmc_traffic.json` | HBM-side bytes per launch per kernel class from two separate PMC passes (`rocprofv3 --pmc FETCH_SIZE --kernel-trace`, `--pmc WRITE_SIZE --kernel-trace`, each around `bench.py --steps 3 --warmup 1`), reduced by `tools/pmc_traffic.py`: `FETCH_SIZE*2*1024 + WRITE_SIZE*1024` (KiB units; gfx950 FETCH_SIZE counts 128-B requests as 64 B — MI355X_MICROARCH.md §HBM).  `bench.py` reads it for `roofline.traffic`. |
 | `{tag}_pmc_l2_step.json` | a fourth PMC pass (`--pmc TCC_HIT TCC_MISS TCC_REQ --kernel-trace`, `tools/pmc_l2_step.sh`): L2 hit rate and miss bytes per launch per kernel class, in situ over whole steps |
 | `{tag}_pmc_mfma_util.json` | a third PMC pass (`--pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_BUSY_CYCLES SQ_WAVE_CYCLES --kernel-trace`): per kernel symbol `SQ_VALU_MFMA_BUSY_CYCLES / (GRBM_GUI_ACTIVE/8 x 1024 SIMDs)` summed over its launches (busy = 16 cycles per 16x16x32 MFMA, 32 per 32x32x16; calibrated with `tools/ubench/mfma_rate.hip`) |
 
 Commands (as the guide prescribes, counters in their own passes): `cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT &&
-rocprofv3 --kernel-trace --stats -d <out> -o {tag} --output-format csv -- python bench.py --steps 10 --warmup 2 --no-cpu-baseline`.
+rocprofv3 --kernel-trace --stats -d <out> -o {tag} --output-format csv -- python bench.py --full --steps 10 --warmup 2 --no-cpu-baseline`.
 
 ## Headline (un-profiled, `{tag}_bench_default.json`)
 

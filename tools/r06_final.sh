@@ -17,10 +17,10 @@ profiles)
 lines)
   for cfg in "cfg2 --direction render --batch 2 --latent 32 --dtype bf16" "cfg5 --batch 1 --latent 128"; do
     set -- $cfg; name=$1; shift
-    timeout 400 python bench.py --no-cpu-baseline --no-loop "$@" > $O/final_bench_$name.json 2> $O/final_bench_$name.err
+    timeout 400 python bench.py --full --no-cpu-baseline --no-loop "$@" > $O/final_bench_$name.json 2> $O/final_bench_$name.err
   done
   for b in 5 8 10 20; do
-    timeout 300 python bench.py --no-cpu-baseline --no-loop --no-live-traffic --batch $b > $O/final_bench_b$b.json 2>/dev/null
+    timeout 300 python bench.py --full --no-cpu-baseline --no-loop --no-live-traffic --batch $b > $O/final_bench_b$b.json 2>/dev/null
   done
   timeout 600 python tools/loop_bench.py > $O/final_loop_bench.json 2>/dev/null
   timeout 300 python tools/hoist_bench.py --shape-table $O/final_hoist_shapes.json > $O/final_hoist_bench.json 2>/dev/null
