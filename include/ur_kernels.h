@@ -42,7 +42,7 @@
 extern "C" {
 #endif
 
-#define UR_ABI_VERSION 12
+#define UR_ABI_VERSION 13
 
 #define UR_E_BADARG (-1001)   /* inconsistent descriptor (shape / alignment / null pointer)   */
 #define UR_E_UNSUPPORTED (-1002) /* shape outside what the kernels are instantiated for       */
@@ -247,7 +247,9 @@ int64_t ur_igemm_partial_floats(const ur_igemm_desc* d);
 
 /*
  * GroupNorm over NHWC, optionally over the concatenation of two sources (x0 | x1), optional SiLU.
- *   stats:  partial[b][chunk][g][2] = (sum, sumsq) over the rows of that chunk, fp32.
+ *   stats:  partial[b][chunk][g][2] = (sum, sumsq) of x - K over the rows of that chunk, fp32 (ABI 13: pivot-shifted).
+ *           K = the hi part of the group's first element (row 0 of sample b, channel g * cpg of x0 | x1); every consumer of
+ *           `partial` re-reads it: mean = K + sum / n, var = sumsq / n - (sum / n)^2 -- no cancellation when |mean| >> std.
  *   apply:  y = (x - mean) * rstd * gamma + beta  (-> SiLU), mean/rstd reduced (fixed order) from the
  *           `nstat` chunks of `partial` written by the stats pass.
  * rows = H*W per sample; nchunks = number of row chunks per sample (grid.x) of the call at hand.
@@ -262,8 +264,8 @@ int ur_groupnorm_apply(const void* x0, const void* x1, const void* x0_lo, const 
                        const float* beta, float eps, int silu, int bper, int pstride, void* out, int dtype,
                        void* stream);
 
-/* The same GroupNorm in ONE launch (one workgroup per (sample, group); statistics over the hi parts, normalisation of
- * hi + lo): for the maps of the deep levels, where stats + apply are launch-bound.  Group width (c0 + c1) / groups must be
+/* The same GroupNorm in ONE launch (one workgroup per (sample, group); pivot-shifted statistics and normalisation
+ * of hi + lo): for the maps of the deep levels, where stats + apply are launch-bound.  Group width (c0 + c1) / groups must be
  * even and <= 128 (UR_E_UNSUPPORTED otherwise).  Strips of at most 4 (16-byte pieces) / 8 (8- / 4-byte pieces) pieces per
  * thread are loaded once and stay in registers across the block reduction (round 6: one memory round trip); larger ones take
  * two sweeps, the second out of L2.  `silu`: bit 0 = SiLU after the affine map; bit 1 (UR_GN_TWO_SWEEP) = always the two-sweep

@@ -46,6 +46,48 @@ def test_tiny_dual_stream_step_vs_oracle(dev, dtype, tol):
     _check_step(out_p, out_o, tol, tol * 2)
 
 
+def _stress(oracle, x, ehs, seed):
+    """Realistic ranges on top of default init (in place): a common bias of +-100 .. 300 on a few resnet conv2 (the residual
+    stream then carries group-wide offsets into the next GroupNorms), 1 % of the output channels of the resnets' conv1 and
+    of the first proj_in of a block scaled x30 .. x100, CLIP-like text-token norms of 28 .. 33, x_t clipped at 4 sigma; then every
+    parameter rounded to fp16 so the oracle and the product hold the same weights."""
+    g = torch.Generator().manual_seed(seed)
+    with torch.no_grad():
+        for net in oracle:
+            mods = [(n, m) for n, m in net.named_modules() if isinstance(m, (torch.nn.Conv2d, torch.nn.Linear))]
+            for i, (n, m) in enumerate([(n, m) for n, m in mods if n.endswith("resnets.0.conv2")][:3]):
+                m.bias += (-1) ** i * (100 + 200 * torch.rand(1, generator=g).item())
+            # outlier channels where a norm follows: the resnets' conv1 (-> norm2) and the attentions' proj_in (-> norm1)
+            for n, m in [(n, m) for n, m in mods if n.endswith("conv1") or n.endswith("attentions.0.proj_in")]:
+                k = max(1, m.weight.shape[0] // 100)
+                rows = torch.randperm(m.weight.shape[0], generator=g)[:k]
+                m.weight[rows] *= 30 + 70 * torch.rand(k, *[1] * (m.weight.dim() - 1), generator=g)
+            for p_ in net.parameters():
+                p_.data = p_.data.to(torch.float16).to(torch.float32)
+    ehs = ehs / ehs.norm(dim=-1, keepdim=True) * (28 + 5 * torch.rand(*ehs.shape[:-1], 1, generator=g))
+    return x.clamp(-4, 4), ehs
+
+
+@pytest.mark.parametrize("dtype,tol", [(torch.float16, 3e-3), (torch.bfloat16, 2.5e-2)])
+def test_tiny_dual_stream_step_vs_oracle_stressed(dev, dtype, tol):
+    """test_tiny_dual_stream_step_vs_oracle on stressed weights and inputs (_stress), every output finite.  The exchange
+    tensors keep the normal test's bound; img_pred / attr_pred get 1.5x it: measured 3.17e-3 / 1.6e-3 (fp16) and 2.58e-2 /
+    1.25e-2 (bf16) with the pivot-shifted GroupNorm statistics.  The residual stream then holds |x| up to ~600, where one
+    fp16 / bf16 storage rounding of the activations that are not (hi, lo) pairs costs ulp(offset) against a unit spread;
+    the error has not been attributed to single operations yet."""
+    oracle = O.build_triplet(O.TINY_CONFIG, seed=1234)
+    x, c, ehs, ti, ta = O.make_inputs(2, 16, 64, seed=99)
+    x, ehs = _stress(oracle, x, ehs, seed=5)
+    out_o = O.dual_stream_step(*oracle, x, c, ehs, ti, ta)
+    unet, enc, dec = build_product_from_oracle(*oracle, dtype, dev)
+    with torch.no_grad():
+        out_p = product_step(unet, enc, dec, x.to(dev), c.to(dev), ehs.to(dev), ti.to(dev), ta.to(dev))
+    for k, v in out_p.items():
+        for t in (v if isinstance(v, (list, tuple)) else [v]):
+            assert t is None or bool(torch.isfinite(t.float()).all()), k
+    _check_step(out_p, out_o, tol * 1.5, tol * 2)
+
+
 def test_tiny_matches_committed_golden(dev):
     """The committed golden vectors (tests/golden/make_golden.py) pin the oracle; the GPU must match them too."""
     from safetensors.torch import load_file

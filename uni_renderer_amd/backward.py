@@ -230,11 +230,21 @@ class GradSink:
 grad_sink = GradSink()
 
 
-def cast_many(srcs, dtype, sumsq: bool = False, packed: bool = False, outs=None):
+def cast_sumsq_floats(numels) -> int:
+    """Length of the sums-of-squares output of ``cast_many(..., sumsq=True)`` over <= 128 tensors of these sizes."""
+    arr = (_CastDesc * len(numels))()
+    for k, n in enumerate(numels):
+        arr[k].n = int(n)
+    return int(_lib.load().ur_cast_multi_blocks(arr, len(numels)))
+
+
+def cast_many(srcs, dtype, sumsq: bool = False, packed: bool = False, outs=None, sumsq_out=None):
     """``[s.to(dtype) for s in srcs]`` for fp32 -> fp16 / bf16 or fp16 / bf16 -> fp32, 128 tensors per launch
     (``ur_cast_multi``).  ``sumsq`` (to fp32 only): also returns the per-workgroup sums of squares of everything written,
     one 1-D fp32 tensor (``ur_cast_multi_sumsq``).  ``outs``: write into these contiguous tensors (entries may be None:
-    allocated here) instead of fresh ones -- the gradient views of a bucket (GradSink)."""
+    allocated here) instead of fresh ones -- the gradient views of a bucket (GradSink).  ``sumsq_out``: write the sums of
+    squares into this fp32 tensor of ``cast_sumsq_floats`` elements (<= 128 sources: one launch) instead of a fresh one --
+    a fixed address that a captured clipping step can read."""
     lib = _lib.load()
     srcs = [s_.contiguous() for s_ in srcs]
     if outs is not None:
@@ -271,7 +281,13 @@ def cast_many(srcs, dtype, sumsq: bool = False, packed: bool = False, outs=None)
         for k, (a, b) in enumerate(part):
             arr[k].src, arr[k].dst, arr[k].n = a.data_ptr(), b.data_ptr(), a.numel()
         if sumsq and to_f32:
-            ps = torch.empty(int(lib.ur_cast_multi_blocks(arr, len(part))), dtype=torch.float32, device=srcs[0].device)
+            nb = int(lib.ur_cast_multi_blocks(arr, len(part)))
+            if sumsq_out is not None:
+                if len(srcs) > 128 or sumsq_out.dtype != torch.float32 or sumsq_out.numel() != nb or not sumsq_out.is_contiguous():
+                    raise ValueError("cast_many(sumsq_out=...): a contiguous fp32 tensor of cast_sumsq_floats() elements")
+                ps = sumsq_out
+            else:
+                ps = torch.empty(nb, dtype=torch.float32, device=srcs[0].device)
             check(lib.ur_cast_multi_sumsq(arr, len(part), 1, DT[low], ps.data_ptr(), st), "ur_cast_multi_sumsq")
             partials.append(ps)
         else:

@@ -363,8 +363,8 @@ __global__ void __launch_bounds__(256) geglu_bwd_kernel(const T* __restrict__ h,
 // Thread mapping as in the forward kernels: a thread owns one 8-channel vector and strides over rows.  C <= 2048.
 // ---------------------------------------------------------------------------------------------------------------
 template <typename T>
-__device__ __forceinline__ void gn_stat_reduce(const float* __restrict__ partial, int b, int nstat, int groups, int rows,
-                                               int cpg, float eps, float2* stat, float2 (*red)[64], int t) {
+__device__ __forceinline__ void gn_stat_reduce(const T* __restrict__ x, int C, const float* __restrict__ partial, int b, int nstat,
+                                               int groups, int rows, int cpg, float eps, float2* stat, float2 (*red)[64], int t) {
     const int g = t & 63, j = t >> 6;
     float s = 0.f, ss = 0.f;
     if (g < groups) {
@@ -381,9 +381,9 @@ __device__ __forceinline__ void gn_stat_reduce(const float* __restrict__ partial
         float2 a0 = red[0][t], a1 = red[1][t], a2 = red[2][t], a3 = red[3][t];
         const float sum = (a0.x + a1.x) + (a2.x + a3.x), sq = (a0.y + a1.y) + (a2.y + a3.y);
         const float n = (float)rows * (float)cpg;
-        const float mean = sum / n;
-        const float var = fmaxf(sq / n - mean * mean, 0.f);
-        stat[t] = make_float2(mean, rsqrtf(var + eps));
+        const float m1 = sum / n;  // partials are pivot-shifted (ur_groupnorm_stats): mean = K + m1
+        const float var = fmaxf(sq / n - m1 * m1, 0.f);
+        stat[t] = make_float2(gn_pivot(x, x, C, 0, b, rows, t * cpg) + m1, rsqrtf(var + eps));
     }
     __syncthreads();
 }
@@ -400,7 +400,7 @@ __global__ void __launch_bounds__(256) gn_bwd_reduce_kernel(const T* __restrict_
     __shared__ float2 acc[256];  // one entry per thread = (row lane, vector column), folded per channel below
     const int nvec = C >> 3, cpg = C / groups;
     const int b = blockIdx.y, chunk = blockIdx.x, t = threadIdx.x;
-    gn_stat_reduce<T>(partial, b, nstat, groups, rows, cpg, eps, stat, red, t);
+    gn_stat_reduce<T>(x, C, partial, b, nstat, groups, rows, cpg, eps, stat, red, t);
     const int rpc = (rows + nchunks - 1) / nchunks;
     const int rbeg = chunk * rpc, rend = min(rows, rbeg + rpc);
     const int tpr = min(nvec, 256), rs = 256 / tpr;
@@ -508,14 +508,19 @@ __global__ void __launch_bounds__(GNB_THREADS) gn_bwd_fused_kernel(const T* __re
     const T* db = dy + (int64_t)b * rows * C + c0;
     T* ob = dx + (int64_t)b * rows * C + c0;
 
-    // ---- sweep 1: statistics of the strip ----
+    // ---- sweep 1: statistics of the strip, shifted by the group's pivot as in the forward (gn_pivot) ----
+    const float kp = gn_pivot(x, x, C, 0, b, rows, g * cpg);
     float s1 = 0.f, s2 = 0.f;
     if (active) {
         for (int r = r0; r < rows; r += R) {
             float v[P];
             gnb_load<T, P>(xb + (int64_t)r * C, v);
 #pragma unroll
-            for (int k = 0; k < P; ++k) { s1 += v[k]; s2 += v[k] * v[k]; }
+            for (int k = 0; k < P; ++k) {
+                v[k] -= kp;
+                s1 += v[k];
+                s2 += v[k] * v[k];
+            }
         }
     }
     s1 = wave_sum(s1);
@@ -526,8 +531,9 @@ __global__ void __launch_bounds__(GNB_THREADS) gn_bwd_fused_kernel(const T* __re
     float sum = 0.f, sq = 0.f;
 #pragma unroll
     for (int w = 0; w < GNB_THREADS / 64; ++w) { sum += red[w].x; sq += red[w].y; }  // fixed order
-    const float mean = sum / n;
-    const float rstd = rsqrtf(fmaxf(sq / n - mean * mean, 0.f) + eps);
+    const float m1 = sum / n;
+    const float mean = kp + m1;
+    const float rstd = rsqrtf(fmaxf(sq / n - m1 * m1, 0.f) + eps);
 
     float gm[P], bt[P];
 #pragma unroll
@@ -638,7 +644,7 @@ __global__ void __launch_bounds__(256) gn_bwd_apply_kernel(const T* __restrict__
     __shared__ float2 gpart[256];
     const int nvec = C >> 3, cpg = C / groups;
     const int b = blockIdx.y, chunk = blockIdx.x, t = threadIdx.x;
-    gn_stat_reduce<T>(partial, b, nstat, groups, rows, cpg, eps, stat, red, t);
+    gn_stat_reduce<T>(x, C, partial, b, nstat, groups, rows, cpg, eps, stat, red, t);
     {   // per group sums of gamma_c * (sum dz, sum dz*xhat): 4 threads per group over its channels and the nred chunks
         const int g = t >> 2, q = t & 3;
         float a = 0.f, a2 = 0.f;

@@ -584,7 +584,7 @@ __global__ void __launch_bounds__(RGN_THREADS) igemm_splitk_reduce_gn(const ur_i
     const float* biasz = p.bias ? p.bias + (int64_t)zb * p.zbias : nullptr;
     const T* rowz = p.rowadd ? reinterpret_cast<const T*>(p.rowadd) + (int64_t)zb * p.zrow + (int64_t)b * p.ld_rowadd : nullptr;
     float v[RGN_MAXQ][4];
-    float s1 = 0.f, s2 = 0.f;
+    float s1 = 0.f;
 #pragma unroll
     for (int i = 0; i < RGN_MAXQ; ++i) {
         const int e = threadIdx.x + i * RGN_THREADS;
@@ -604,20 +604,36 @@ __global__ void __launch_bounds__(RGN_THREADS) igemm_splitk_reduce_gn(const ur_i
                 x[k] = to_f(from_f<T>(x[k] * p.out_scale));  // what the unfused path stores and GroupNorm re-reads
                 v[i][k] = x[k];
                 s1 += x[k];
-                s2 = fmaf(x[k], x[k], s2);
             }
         }
     }
+    // exact two-pass statistics (the strip is in registers): the mean, then the sum of squared deviations from it -- no
+    // cancellation when the group's mean is large against its spread
     s1 = wave_sum(s1);
-    s2 = wave_sum(s2);
-    if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = s1; red[1][threadIdx.x >> 6] = s2; }
+    if ((threadIdx.x & 63) == 0) red[0][threadIdx.x >> 6] = s1;
     __syncthreads();
-    float t1 = 0.f, t2 = 0.f;
+    float t1 = 0.f;
 #pragma unroll
-    for (int w = 0; w < RGN_THREADS / 64; ++w) { t1 += red[0][w]; t2 += red[1][w]; }
+    for (int w = 0; w < RGN_THREADS / 64; ++w) t1 += red[0][w];
     const float n = (float)rows * (float)cpg;
     const float mean = t1 / n;
-    const float rstd = rsqrtf(fmaxf(t2 / n - mean * mean, 0.f) + eps);
+    float s2 = 0.f;
+#pragma unroll
+    for (int i = 0; i < RGN_MAXQ; ++i)
+        if (threadIdx.x + i * RGN_THREADS < nq) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const float d = v[i][k] - mean;
+                s2 = fmaf(d, d, s2);
+            }
+        }
+    s2 = wave_sum(s2);
+    if ((threadIdx.x & 63) == 0) red[1][threadIdx.x >> 6] = s2;
+    __syncthreads();
+    float t2 = 0.f;
+#pragma unroll
+    for (int w = 0; w < RGN_THREADS / 64; ++w) t2 += red[1][w];
+    const float rstd = rsqrtf(t2 / n + eps);
     const float* gz = gamma + (int64_t)zb * zgn;
     const float* bz = beta + (int64_t)zb * zgn;
     T* outz = reinterpret_cast<T*>(p.out) + (int64_t)zb * p.zout;

@@ -18,7 +18,7 @@ namespace ur {
 
 // ------------------------------------------------------------------------------------------
 // GroupNorm statistics.  grid = (nchunks, B); a workgroup sums rows [chunk*rpc, (chunk+1)*rpc) of
-// sample b over all channels and writes partial[b][chunk][g] = (sum, sumsq).
+// sample b over all channels and writes partial[b][chunk][g] = (sum, sumsq) of x - K, K = the group's pivot (gn_pivot).
 // Thread mapping: a thread owns one 8-channel vector (fixed) and strides over rows, so consecutive
 // threads read consecutive 16-B pieces of a row and, because NHWC rows are contiguous, of the next row.
 // Eight row loads are always in flight per thread (rows past the chunk are clamped and weighted 0), a
@@ -45,6 +45,9 @@ __global__ void __launch_bounds__(256) gn_stats_kernel(const T* __restrict__ x0,
     const int rs = 256 / tpr;
     const int rsub = t / tpr, cvl = t - rsub * tpr;
     const int nv0 = c0 >> 3;
+    __shared__ float piv[64];  // pivot of every group of sample b
+    if (t < groups) piv[t] = gn_pivot(x0, x1, c0, c1, b, rows, t * cpg);
+    __syncthreads();
     float gs = 0.f, gss = 0.f;  // threads 4g .. 4g+3 accumulate group g over the passes
     for (int cvb = 0; cvb < nvec; cvb += tpr) {
         const int cv = cvb + cvl;
@@ -53,6 +56,9 @@ __global__ void __launch_bounds__(256) gn_stats_kernel(const T* __restrict__ x0,
         for (int i = 0; i < 8; ++i) { s[i] = 0.f; ss[i] = 0.f; }
         const bool active = rsub < rs && cv < nvec && rbeg < rend;
         if (active) {
+            float kp[8];  // pivot of each of the 8 channels' group
+#pragma unroll
+            for (int i = 0; i < 8; ++i) kp[i] = piv[(cv * 8 + i) / cpg];
             const T* base;
             const lo_t<T>* lbase;  // low part of a (hi, lo) residual-stream input, or null
             int64_t ld;
@@ -73,7 +79,7 @@ __global__ void __launch_bounds__(256) gn_stats_kernel(const T* __restrict__ x0,
                         const float w = (r + u * rs < rend) ? 1.f : 0.f;
 #pragma unroll
                         for (int i = 0; i < 8; ++i) {
-                            const float v = ((float)raw[u][i] + rlo[u][i]) * w;
+                            const float v = ((float)raw[u][i] + rlo[u][i] - kp[i]) * w;
                             s[i] += v;
                             ss[i] += v * v;
                         }
@@ -85,7 +91,7 @@ __global__ void __launch_bounds__(256) gn_stats_kernel(const T* __restrict__ x0,
                     const float w = (r + u * rs < rend) ? 1.f : 0.f;
 #pragma unroll
                     for (int i = 0; i < 8; ++i) {
-                        const float v = (float)raw[u][i] * w;
+                        const float v = ((float)raw[u][i] - kp[i]) * w;
                         s[i] += v;
                         ss[i] += v * v;
                     }
@@ -194,9 +200,9 @@ __global__ void __launch_bounds__(256) gn_apply_kernel(const T* __restrict__ x0,
             float2 a0 = red[0][t], a1 = red[1][t], a2 = red[2][t], a3 = red[3][t];
             const float sum = (a0.x + a1.x) + (a2.x + a3.x), sq = (a0.y + a1.y) + (a2.y + a3.y);
             const float n = (float)rows * (float)cpg;
-            const float mean = sum / n;
-            const float var = fmaxf(sq / n - mean * mean, 0.f);
-            stat[t] = make_float2(mean, rsqrtf(var + eps));
+            const float m1 = sum / n;  // mean - K
+            const float var = fmaxf(sq / n - m1 * m1, 0.f);
+            stat[t] = make_float2(gn_pivot(x0, x1, c0, c1, b, rows, t * cpg) + m1, rsqrtf(var + eps));
         }
     }
     __syncthreads();
@@ -209,7 +215,7 @@ __global__ void __launch_bounds__(256) gn_apply_kernel(const T* __restrict__ x0,
     if (rsub >= rs || rbeg >= rend) return;
     const int poff = bper > 0 ? (b / bper) * pstride : 0;  // per-stream affine parameters (grouped execution)
     for (int cv = cvl; cv < nvec; cv += tpr) {
-        float a[8], sh[8];
+        float a[8], mu[8], sh[8];
         {
             const float4* g4 = reinterpret_cast<const float4*>(gamma + poff + cv * 8);
             const float4* b4 = reinterpret_cast<const float4*>(beta + poff + cv * 8);
@@ -222,7 +228,9 @@ __global__ void __launch_bounds__(256) gn_apply_kernel(const T* __restrict__ x0,
             for (int i = 0; i < 8; ++i) {
                 const float2 st = (cpg < 8) ? stat[(ca + i) / cpg] : ((i < split) ? sa : sb);
                 a[i] = st.y * gm[i];
-                sh[i] = bt[i] - st.x * a[i];
+                mu[i] = st.x;
+                sh[i] = bt[i];  // (x - mean) * a + beta: a folded beta - mean * a would lose |mean * a| * 2^-24 (a constant
+                                // group of mean 300 at rstd = 1 / sqrt(eps) would not come out as beta)
             }
         }
         const T* base;
@@ -251,7 +259,7 @@ __global__ void __launch_bounds__(256) gn_apply_kernel(const T* __restrict__ x0,
                     float v[8];
 #pragma unroll
                     for (int i = 0; i < 8; ++i) {
-                        const float y = ((float)raw[u][i] + rlo[u][i]) * a[i] + sh[i];
+                        const float y = ((float)raw[u][i] + rlo[u][i] - mu[i]) * a[i] + sh[i];
                         v[i] = silu ? silu_f(y) : y;
                     }
                     store8(ob + (int64_t)(r + u * rs) * C, v);
@@ -410,7 +418,7 @@ __global__ void __launch_bounds__(256) layernorm5_kernel(const T* __restrict__ x
 
 // ---------------------------------------------------------------------------------------------------------------
 // One-launch GroupNorm(+SiLU) for the small maps (deep levels): one workgroup per (sample, group) makes two sweeps
-// over its [rows][cpg] strip -- sums over the hi parts, then normalise hi + lo -- the second sweep finds the strip in
+// over its [rows][cpg] strip -- pivot-shifted sums of hi + lo, then normalise hi + lo -- the second sweep finds the strip in
 // this XCD's L2.  Replaces stats + apply (two launches, a partials round trip) where those are launch-bound: 12.6 us
 // for a 1.3 MB map against ~3 us of traffic.  A thread walks (row, piece) pairs, a piece = P channels (2 / 4 / 8
 // by the divisibility of the group width); the fixed-order block reduction keeps the result deterministic.
@@ -462,7 +470,7 @@ __global__ void __launch_bounds__(GNF_THREADS) gn_fused_kernel(const T* __restri
                                                        const float* __restrict__ beta, float eps, int silu, int bper,
                                                        int pstride, T* __restrict__ out, int xcd) {
     __shared__ float2 red[GNF_THREADS / 64];
-    __shared__ __attribute__((aligned(16))) float2 aff[128];  // per channel of the group: (gamma * rstd, beta - mean * gamma * rstd)
+    __shared__ __attribute__((aligned(16))) float2 aff[128];  // per channel of the group: (gamma * rstd, beta), y = (x - mean) * a + beta
     // a group's strip is cpg * 2 bytes of every 128-byte line it touches: neighbouring groups share lines.  xcd: consecutive
     // logical ids (groups of one sample) on ONE XCD, so a line is fetched into one L2 instead of two or three
     const int lid_ = xcd ? xcd_remap(blockIdx.x + gridDim.x * blockIdx.y, gridDim.x * gridDim.y) : blockIdx.x + gridDim.x * blockIdx.y;
@@ -473,6 +481,7 @@ __global__ void __launch_bounds__(GNF_THREADS) gn_fused_kernel(const T* __restri
     const int64_t row0 = (int64_t)b * rows;
     constexpr int U = 4;  // independent loads in flight per thread
 
+    const float kp = gn_pivot(x0, x1, c0, c1, b, rows, g * cpg);  // statistics of x - kp (gn_pivot), hi + lo
     float s1 = 0.f, s2 = 0.f;
     {
         int r = t / ppr, pc = t - (t / ppr) * ppr;
@@ -484,12 +493,18 @@ __global__ void __launch_bounds__(GNF_THREADS) gn_fused_kernel(const T* __restri
                 const bool ok = i + GNF_THREADS * u < total;
                 const int rc = ok ? rr : 0;
                 const int c = g * cpg + (ok ? pp : 0) * P;
-                const T* src = c < c0 ? x0 + (row0 + rc) * c0 + c : x1 + (row0 + rc) * c1 + (c - c0);
-                load_piece<T, P>(src, v[u]);
-                if (!ok) {
+                const bool first = c < c0;
+                const int64_t off = first ? (row0 + rc) * c0 + c : (row0 + rc) * c1 + (c - c0);
+                load_piece<T, P>((first ? x0 : x1) + off, v[u]);
+                const lo_t<T>* lo = first ? x0_lo : x1_lo;
+                if (lo) {
+                    float w[P];
+                    load_lo<P>(lo + off, w);
 #pragma unroll
-                    for (int k = 0; k < P; ++k) v[u][k] = 0.f;
+                    for (int k = 0; k < P; ++k) v[u][k] += w[k];
                 }
+#pragma unroll
+                for (int k = 0; k < P; ++k) v[u][k] = ok ? v[u][k] - kp : 0.f;
                 rr += dr; pp += dp;
                 if (pp >= ppr) { pp -= ppr; rr += 1; }
             }
@@ -508,13 +523,11 @@ __global__ void __launch_bounds__(GNF_THREADS) gn_fused_kernel(const T* __restri
     float sum = 0.f, sq = 0.f;
 #pragma unroll
     for (int w = 0; w < GNF_THREADS / 64; ++w) { sum += red[w].x; sq += red[w].y; }  // fixed order
-    const float mean = sum / n;
-    const float rstd = rsqrtf(fmaxf(sq / n - mean * mean, 0.f) + eps);
+    const float m1 = sum / n;
+    const float mean = kp + m1;
+    const float rstd = rsqrtf(fmaxf(sq / n - m1 * m1, 0.f) + eps);
     const int poff = bper > 0 ? (b / bper) * pstride : 0;  // per-stream affine parameters (grouped execution)
-    if (t < cpg) {
-        const float a = gamma[poff + g * cpg + t] * rstd;
-        aff[t] = make_float2(a, beta[poff + g * cpg + t] - mean * a);
-    }
+    if (t < cpg) aff[t] = make_float2(gamma[poff + g * cpg + t] * rstd, beta[poff + g * cpg + t]);
     __syncthreads();
 
     int r = t / ppr, pc = t - (t / ppr) * ppr;
@@ -550,7 +563,7 @@ __global__ void __launch_bounds__(GNF_THREADS) gn_fused_kernel(const T* __restri
 #pragma unroll
             for (int k = 0; k < P; ++k) {
                 const float2 ab = aff[cs[u] - g * cpg + k];
-                float z = fmaf(v[u][k], ab.x, ab.y);
+                float z = fmaf(v[u][k] - mean, ab.x, ab.y);
                 if (silu) z = silu_f(z);
                 y[k] = z;
             }
@@ -562,8 +575,8 @@ __global__ void __launch_bounds__(GNF_THREADS) gn_fused_kernel(const T* __restri
 // Register-resident variant of the one-launch GroupNorm (round 6): when a (sample, group) strip is at most NP pieces per thread,
 // every piece (hi AND lo) is loaded ONCE, all loads issued back to back, kept as raw bits in registers across the block
 // reduction, then normalised and stored -- one memory round trip instead of two (the second sweep of gn_fused_kernel re-read
-// the strip from L2: on these 5-12 us launches a dependent round trip is 1-2 us).  Statistics over the hi parts only, in the
-// same per-thread order and the same block reduction as gn_fused_kernel: results are bit-identical to it.
+// the strip from L2: on these 5-12 us launches a dependent round trip is 1-2 us).  Statistics of hi + lo in the same
+// per-thread order and the same block reduction as gn_fused_kernel: results are bit-identical to it.
 template <typename T, int P> struct RawPiece;
 template <typename T> struct RawPiece<T, 8> { uint4 v; };
 template <typename T> struct RawPiece<T, 4> { uint2 v; };
@@ -631,15 +644,26 @@ __global__ void __launch_bounds__(GNF_THREADS) gn_resident_kernel(const T* __res
         for (int u = 0; u < NP; ++u)
             lo[u].v = *reinterpret_cast<const decltype(lo[u].v)*>(lsrc + piece_off(min(t + u * GNF_THREADS, total - 1)));
     }
-    // statistics over the hi parts, pieces in gn_fused_kernel's per-thread order (i = t, t + 1024, ...)
+    // statistics of hi + lo - kp, pieces in gn_fused_kernel's per-thread order (i = t, t + 1024, ...)
+    const float kp = gn_pivot(x0, x1, c0, c1, b, rows, g * cpg);
     float s1 = 0.f, s2 = 0.f;
 #pragma unroll
     for (int u = 0; u < NP; ++u) {
         if (t + u * GNF_THREADS < total) {
             float v[P];
             unpack_piece<T, P>(hi[u], v);
+            if (lsrc) {
+                float w[P];
+                unpack_lo<lo_t<T>, P>(lo[u], w);
 #pragma unroll
-            for (int k = 0; k < P; ++k) { s1 += v[k]; s2 += v[k] * v[k]; }
+                for (int k = 0; k < P; ++k) v[k] += w[k];
+            }
+#pragma unroll
+            for (int k = 0; k < P; ++k) {
+                v[k] -= kp;
+                s1 += v[k];
+                s2 += v[k] * v[k];
+            }
         }
     }
     s1 = wave_sum(s1);
@@ -650,13 +674,11 @@ __global__ void __launch_bounds__(GNF_THREADS) gn_resident_kernel(const T* __res
     float sum = 0.f, sq = 0.f;
 #pragma unroll
     for (int w = 0; w < GNF_THREADS / 64; ++w) { sum += red[w].x; sq += red[w].y; }  // fixed order
-    const float mean = sum / n;
-    const float rstd = rsqrtf(fmaxf(sq / n - mean * mean, 0.f) + eps);
+    const float m1 = sum / n;
+    const float mean = kp + m1;
+    const float rstd = rsqrtf(fmaxf(sq / n - m1 * m1, 0.f) + eps);
     const int poff = bper > 0 ? (b / bper) * pstride : 0;
-    if (t < cpg) {
-        const float a = gamma[poff + g * cpg + t] * rstd;
-        aff[t] = make_float2(a, beta[poff + g * cpg + t] - mean * a);
-    }
+    if (t < cpg) aff[t] = make_float2(gamma[poff + g * cpg + t] * rstd, beta[poff + g * cpg + t]);
     __syncthreads();
     // keep the strip as RAW bits across the reduction: without this the compiler holds the unpacked floats of the statistics
     // pass alive (2-4x the registers) and the larger instantiations spill
@@ -681,7 +703,7 @@ __global__ void __launch_bounds__(GNF_THREADS) gn_resident_kernel(const T* __res
 #pragma unroll
             for (int k = 0; k < P; ++k) {
                 const float2 ab = aff[pc * P + k];
-                float z = fmaf(v[k], ab.x, ab.y);
+                float z = fmaf(v[k] - mean, ab.x, ab.y);
                 if (silu) z = silu_f(z);
                 y[k] = z;
             }

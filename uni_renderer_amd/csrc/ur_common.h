@@ -146,6 +146,16 @@ __device__ __forceinline__ void store_lo8(lo_t<T>* p, const float (&v)[8]) {
     else { uint4 r; __builtin_memcpy(&r, b, 16); *reinterpret_cast<uint4*>(p) = r; }
 }
 
+// GroupNorm statistics are PIVOT-SHIFTED sums: sum(x - K) and sum((x - K)^2) with K = the hi part of the group's first
+// element (row 0, first channel of the group), mean = K + s1 / n, var = s2 / n - (s1 / n)^2.  K lies within a few standard
+// deviations of the mean, so the variance does not cancel when a group's mean is large against its spread (the plain
+// sumsq / n - mean^2 loses (mean / std)^2 * 2^-24 relative).  Every kernel that takes or consumes the statistics of a group
+// derives K from the hi tensor alone with this function, so producers and consumers agree on it bit for bit.
+template <typename T>
+__device__ __forceinline__ float gn_pivot(const T* x0, const T* x1, int c0, int c1, int b, int rows, int c) {
+    return c < c0 ? to_f(x0[(int64_t)b * rows * c0 + c]) : to_f(x1[(int64_t)b * rows * c1 + (c - c0)]);
+}
+
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);

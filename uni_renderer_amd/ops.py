@@ -664,9 +664,9 @@ def groupnorm(x, gamma, beta, eps, *, x1=None, groups=32, silu=False, nstat=None
     s = _stream()
     e0 = _prof_begin()
     xl, x1l = lo_of(x), lo_of(x1)
-    # The statistics are taken over the hi parts only: the low parts are zero-mean rounding remainders (|lo| <= ulp/2),
-    # their contribution to a mean / variance over >= 10^3 elements is ~1e-6 relative -- not worth a second read.
-    check(lib.ur_groupnorm_stats(_ptr(x), _ptr(x1), None, None, C0, C1, B, rows, groups, nstat, part.data_ptr(),
+    # The statistics are taken over hi + lo, the value normalised: the low parts are rounding remainders (|lo| <= ulp(hi)/2)
+    # whose variance ulp^2 / 12 is NOT negligible once a group's mean is large against its spread (ulp(300) = 0.25 in fp16).
+    check(lib.ur_groupnorm_stats(_ptr(x), _ptr(x1), _ptr(xl), _ptr(x1l), C0, C1, B, rows, groups, nstat, part.data_ptr(),
                                  DT[x.dtype], s), "ur_groupnorm_stats")
     _prof_end(e0, "gn_stats", 0.0, 1.0 * out.numel() * out.element_size())
     e1 = _prof_begin()

@@ -221,6 +221,7 @@ class GradientBuckets:
         # being added into zeroed buckets by autograd; False restores the round-5 protocol (zero + accumulate) for A/B runs
         self.direct_write = True
         self.sumsq_parts: Optional[List[torch.Tensor]] = None  # sums of squares collected by finish()'s copy-back pass
+        self._sumsq: Optional[List[torch.Tensor]] = None  # ... written into these per-bucket buffers (fixed addresses)
         self._comm: List[Optional[torch.Tensor]] = [None] * len(self.buckets)
         self._arrived = [0] * len(self.buckets)
         self._launched = 0
@@ -343,13 +344,28 @@ class GradientBuckets:
                 if buf.is_cuda and bw.FUSED_GRADNORM:
                     # reduced half-precision means -> the fp32 gradients, and the clipping norm's sums of squares from the same
                     # pass (ur_cast_multi_sumsq) instead of another sweep over the 7 GB (train.py:1422)
-                    _, part = bw.cast_many([buf], torch.float32, sumsq=True, outs=[self.flat[bi]])
+                    _, part = bw.cast_many([buf], torch.float32, sumsq=True, outs=[self.flat[bi]], sumsq_out=self.sumsq_buffers()[bi])
                     parts.append(part)
                 else:
                     self.flat[bi].copy_(buf)
         self.sumsq_parts = parts if parts and len(parts) == len(self.flat) else None
         bw.grad_sink.end()
         self._reset()
+
+    def fused_sumsq(self) -> bool:
+        """True when ``finish()`` leaves the clipping norm's sums of squares in ``sumsq_parts`` (half-precision transport on
+        the GPU: they come out of the copy-back cast)."""
+        from . import backward as bw
+        return (self.comm_dtype in (torch.bfloat16, torch.float16) and bool(bw.FUSED_GRADNORM) and self.flat[0].is_cuda
+                and not self._single())
+
+    def sumsq_buffers(self) -> List[torch.Tensor]:
+        """The per-bucket buffers ``finish()`` writes the sums of squares into: the same addresses on every step, so a
+        clipping step captured in a graph (train_step.GraphedTrainStep) reads exactly the norm the eager step computes."""
+        if self._sumsq is None:
+            from . import backward as bw
+            self._sumsq = [torch.empty(bw.cast_sumsq_floats([f.numel()]), dtype=torch.float32, device=f.device) for f in self.flat]
+        return self._sumsq
 
     @torch.no_grad()
     def adopt_all(self) -> int:

@@ -646,6 +646,8 @@ class GraphedTrainStep:
         self.g_up = None
         if self.capture_collectives:
             buckets._reset()
+            if buckets.fused_sumsq():
+                buckets.sumsq_buffers()  # allocated outside the capture: finish() writes them inside it and in eager steps
             before = buckets.launched_from_hooks
             with torch.cuda.graph(self.g_fb):
                 # the hooks fire inside backward(): every complete bucket's collective forks onto RCCL's stream here
@@ -661,9 +663,14 @@ class GraphedTrainStep:
                 _clip_and_update(nets, optimizer, None, max_grad_norm, self.stats)
         if buckets is not None:
             buckets._reset()
+            # the eager finish() before every replay leaves the clipping norm's sums of squares in fixed buffers when the
+            # transport is half precision: capture the update reading them, the norm the eager step uses (a captured
+            # _foreach_norm over the buckets sums in another order, and the clip coefficient would differ in the last bits)
+            buckets.sumsq_parts = buckets.sumsq_buffers() if buckets.fused_sumsq() else None
             self.g_up = torch.cuda.CUDAGraph()
             with torch.cuda.graph(self.g_up):
                 _clip_and_update(nets, optimizer, buckets, max_grad_norm, self.stats)
+            buckets.sumsq_parts = None
 
     def _validate_captured_collectives(self):
         """The split "forked by a hook during the backward" / "launched by finish()" is baked into the graph at capture time.
