@@ -264,7 +264,7 @@ def _attn_ref(q, k, v, H):
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
-@pytest.mark.parametrize("d", [32, 40, 64, 80, 160])
+@pytest.mark.parametrize("d", [32, 40, 64, 80, 128, 160])
 @pytest.mark.parametrize("T", [(64, 64), (200, 77), (256, 256), (16, 16), (130, 333)])
 def test_attention(dev, dtype, d, T):
     from uni_renderer_amd import ops
@@ -299,7 +299,7 @@ def test_attention_fused_qk_layout_and_peaky_softmax(dev, dtype):
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
-@pytest.mark.parametrize("d", [32, 40, 64, 80, 160])
+@pytest.mark.parametrize("d", [32, 40, 64, 80, 128, 160])
 @pytest.mark.parametrize("T", [(256, 256), (200, 77), (128, 40), (1024, 1000)])
 def test_attention_prescaled_log2_scores(dev, dtype, d, T):
     """scale=0: q.k already carries d^-1/2 * log2(e) (folded into the projections by the modules).  For d = 40
