@@ -32,6 +32,10 @@
  *   ur_nchw_to_nhwc / ur_nhwc_to_nchw   layout glue at the module boundary (the reference is NCHW).
  *   ur_ddim_update / ur_unipc_update / ur_sampler_advance   the per-group scheduler `.step()` calls and the timestep bookkeeping between
  *                   two denoise steps of the sampling loops (models/pipeline.py:2691-2730, 1645-1649), on the device.
+ *   ur_freeu        diffusers' apply_freeu in front of `torch.cat([hidden, skip])` of the first two up blocks
+ *                   (models/unet_2d_blocks.py:2343-2370, 2522-2546, 2653-2677, 2767-2790): the in-place backbone scale
+ *                   `hidden[:, : C // 2] *= b` and fourier_filter's fftn -> fftshift -> box * s -> ifftshift -> ifftn -> real
+ *                   of the skip, as one launch without an FFT.
  */
 #ifndef UR_KERNELS_H
 #define UR_KERNELS_H
@@ -42,7 +46,7 @@
 extern "C" {
 #endif
 
-#define UR_ABI_VERSION 13
+#define UR_ABI_VERSION 14
 
 #define UR_E_BADARG (-1001)   /* inconsistent descriptor (shape / alignment / null pointer)   */
 #define UR_E_UNSUPPORTED (-1002) /* shape outside what the kernels are instantiated for       */
@@ -322,6 +326,24 @@ int ur_add(const void* a, const void* b, float alpha, void* out, int64_t n, int 
 /* the same over (hi, lo) pairs: out + out_lo = (a + a_lo) + alpha * (b + b_lo); any *_lo may be NULL */
 int ur_add_hilo(const void* a, const void* a_lo, const void* b, const void* b_lo, float alpha, void* out, void* out_lo,
                 int64_t n, int dtype, void* stream);
+
+/*
+ * FreeU (arXiv 2309.11497; ABI 14): both halves of one apply_freeu call over B NHWC samples of an H x W map, one launch.
+ *   hidden [B][H][W][Ch]: channels [0, Ch / 2) are multiplied by `b` IN PLACE.  hidden_lo (NULL or the low parts): the value
+ *       scaled is hidden + hidden_lo in fp32 and the rounding remainder of the product is written back to hidden_lo.
+ *   skip [B][H][W][Cs] -> skip_out: fourier_filter(skip, threshold = 1, scale = s).  The box [H/2-1 : H/2+1, W/2-1 : W/2+1] of
+ *       the shifted spectrum is the four frequencies (ky, kx) in {-1, 0}^2, so per (sample, channel), with t = 2 pi y / H,
+ *       p = 2 pi x / W:   x' = x + (s - 1) / (H W) * [a0 + a1 cos t + a2 sin t + a3 cos p + a4 sin p + a5 cos(t+p) + a6 sin(t+p)],
+ *       a_k = the sum of x times the same basis function over the map (a0 = sum x).  fp32 sums in a fixed order (bit-reproducible),
+ *       taken around a per-channel pivot; twiddles in fp32 from sincospi.  skip_lo (NULL or low parts) is added to the input,
+ *       skip_out_lo (NULL or low parts) receives the remainder of the output.  skip_out == skip (and skip_out_lo == skip_lo) is
+ *       legal: a workgroup owns whole (sample, 32-channel) columns and reads them completely before it writes.  Maps of up to
+ *       1024 pixels make one memory round trip (the column stays in registers), larger ones read twice.
+ *   Either half is skipped by passing hidden == NULL or skip == NULL (not both).
+ * Any H, W >= 2; H < 2 or W < 2: UR_E_UNSUPPORTED.  Ch % 8 != 0 or Cs % 8 != 0: UR_E_BADARG.
+ */
+int ur_freeu(void* hidden, void* hidden_lo, int Ch, float b, const void* skip, const void* skip_lo, void* skip_out,
+             void* skip_out_lo, int Cs, float s, int B, int H, int W, int dtype, void* stream);
 
 /* ur_add_hilo (alpha = 1) over up to UR_ADD_MULTI_MAX independent tensor triples in ONE launch (ABI 10).  What a sampling
  * loop with a loop-invariant exchange operand runs per step instead of 13 exchange GEMMs: in the inverse-rendering loop

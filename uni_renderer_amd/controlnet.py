@@ -27,7 +27,7 @@ from . import ops
 from .layers import Attention, Conv2d, Ctx, GroupNorm, PackCache, ResnetBlock2D, TimestepEmbedding, f32, pack_conv3x3, \
     pack_matrix, zero_module
 from .modeling_utils import ConfigModelMixin, register_to_config
-from .unet_2d_blocks import UNetMidBlock2DCrossAttn, get_down_block, get_up_block
+from .unet_2d_blocks import FREEU_KEYS, UNetMidBlock2DCrossAttn, freeu_enabled, get_down_block, get_up_block
 
 CIN_PAD = 64  # conv_in reads its 4 / 28 input channels zero-padded to one 64-channel K chunk
 
@@ -296,6 +296,22 @@ class UNet2DConditionModel(_DenoiserBase):
         self.conv_out = Conv2d(boc[0], out_channels, 3, padding=1)
         self._finish_init()
 
+    def enable_freeu(self, s1, s2, b1, b2):
+        """FreeU (arXiv 2309.11497; ref 749-771): every up block gets the four factors; the blocks of stage 1 / 2
+        (``resolution_idx`` 0 / 1) then scale the first half of the backbone channels by ``b1`` / ``b2`` (in place) and the
+        lowest frequencies of each skip by ``s1`` / ``s2`` before every resnet (``ops.freeu``).  Inference only.  A graph
+        captured from this model bakes the factors in: re-capture after toggling (the pipeline does)."""
+        for blk in self.up_blocks:
+            for k, v in zip(FREEU_KEYS, (s1, s2, b1, b2)):
+                setattr(blk, k, v)
+
+    def disable_freeu(self):
+        """ref 773-779."""
+        for blk in self.up_blocks:
+            for k in FREEU_KEYS:
+                if hasattr(blk, k) or getattr(blk, k, None) is not None:
+                    setattr(blk, k, None)
+
     def forward(
         self,
         sample: torch.Tensor,
@@ -326,6 +342,8 @@ class UNet2DConditionModel(_DenoiserBase):
         """The differentiable forward (train_step.unet_forward) behind the reference's signature and return tuple."""
         from . import train_step as TS
 
+        if freeu_enabled(self):
+            raise NotImplementedError(TS.FREEU_AUTOGRAD_MSG)
         dt = _compute_dtype(self.dtype, self.compute_dtype)
         if (down_res is None) != (mid_res is None):
             raise NotImplementedError("T2I-adapter style down_block_additional_residuals without a mid residual")

@@ -31,6 +31,7 @@ from . import ops, tchain
 from .controlnet import CIN_PAD, _compute_dtype
 from .layers import (LOG2E, Attention, BasicTransformerBlock, ResnetBlock2D, Transformer2DModel, f32, geglu_perm,
                      pack_conv3x3, pack_matrix)
+from .unet_2d_blocks import freeu_params
 
 
 # q | k | v of a self-attention as ONE grouped GEMM with a transposed side output for V (ur_igemm_desc.out_vt, ABI 8);
@@ -499,10 +500,18 @@ class GroupedDualStreamStep:
     def _up(self, nets, x, up_skips, ctx):
         """The up blocks of ``nets`` (controlnet.py:1119-1151 / 2480-2512); ``up_skips`` is consumed from its end."""
         temb, tsl, kc, vtc, ksl = ctx
+        Bn = x.shape[0] // len(nets)
         for bi_ in range(len(nets[0].up_blocks)):
             blks = [n.up_blocks[bi_] for n in nets]
+            fus = [freeu_params(b) for b in blks]
             for li, r0 in enumerate(blks[0].resnets):
                 s = up_skips.pop()
+                for ni, fu in enumerate(fus):
+                    # FreeU (unet_2d_blocks.py:2522-2546 of the reference) on the sample rows of the networks that have it on
+                    # (the UNet: rows [0, B) of [unet ; dec]).  Both tensors are this step's own: produced fresh, consumed
+                    # once, so the skip is filtered in place
+                    if fu is not None:
+                        s = ops.freeu(x, s, *fu, out=s, rows=(ni * Bn, (ni + 1) * Bn))
                 x = self._resnet([b.resnets[li] for b in blks], x, temb, tsl[id(r0)], x1=s)
                 if getattr(blks[0], "has_cross_attention", False):
                     tsf = [b.attentions[li] for b in blks]

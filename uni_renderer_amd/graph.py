@@ -72,7 +72,9 @@ def dual_stream_step(unet, enc, dec, x_t, cond, ehs, t_img, t_attr, run_decoder:
 
 class GraphedDualStreamStep:
     """Capture once, replay many times.  ``step(...)`` copies new inputs into the static buffers (device to
-    device, on the replay stream) and launches the graph; the returned tensors are overwritten by the next call."""
+    device, on the replay stream) and launches the graph; the returned tensors are overwritten by the next call.
+    The UNet's FreeU factors (``enable_freeu`` / ``disable_freeu``) are kernel arguments baked into the capture: a direct user
+    must ``capture()`` again after toggling them (``UniRendererPipeline`` keys its graphs on them)."""
 
     def __init__(self, unet, enc, dec, batch: int, latent_hw, cross_dim: int, dtype=torch.float16,
                  device="cuda", run_decoder: bool = True, cond_channels: int = 28, img_channels: int = 4,
@@ -164,7 +166,9 @@ class GraphedHoistedStep:
     the per-step part.  Same buffer names as ``GraphedDualStreamStep`` (``x_t``, ``cond``, ``ehs``, ``t_img``, ``t_attr``);
     inverse direction (``run_decoder``): ``x_t`` / ``t_img`` / ``ehs`` are the fixed inputs and ``cond`` / ``t_attr`` evolve,
     rendering direction: the reverse.  ``hoist=False`` replays the prologue in front of EVERY step -- the un-hoisted loop
-    with the same kernels, what the hoisting is tested against bit for bit."""
+    with the same kernels, what the hoisting is tested against bit for bit.
+    As with ``GraphedDualStreamStep``, the UNet's FreeU factors are baked into the capture: ``capture()`` again after
+    ``enable_freeu`` / ``disable_freeu``."""
 
     def __init__(self, unet, enc, dec, batch: int, latent_hw, cross_dim: int, dtype=torch.float16, device="cuda",
                  run_decoder: bool = True, cond_channels: int = 28, img_channels: int = 4, ctx_len: int = 77,

@@ -822,6 +822,54 @@ def add(a, b, alpha: float = 1.0, hilo=False):
     return out
 
 
+def freeu(hidden, skip, b: float, s: float, *, out=None, rows=None):
+    """One ``apply_freeu`` call of diffusers (FreeU, arXiv 2309.11497) over NHWC tensors, one launch (``ur_freeu``):
+    channels ``[0, C // 2)`` of ``hidden`` are scaled by ``b`` IN PLACE and ``skip`` goes through ``fourier_filter(skip,
+    threshold=1, scale=s)`` -- the four frequencies (ky, kx) in {-1, 0}^2 of every (sample, channel) map are multiplied by
+    ``s``.  Low parts (``hidden.lo`` / ``skip.lo``) are included in the value read; ``hidden.lo`` is rewritten with the
+    remainder of the scaled value and the returned skip carries ``.lo`` if and only if ``skip`` did.  ``out``: where the
+    filtered skip goes (default: a new tensor); ``out=skip`` filters in place.  ``rows = (r0, r1)``: act on samples
+    ``[r0, r1)`` of both tensors only (the rows of one network of a grouped launch); the other samples of an out-of-place
+    ``out`` are then not written.  ``hidden`` or ``skip`` may be None to run one half alone; returns the filtered skip."""
+    ref = skip if skip is not None else hidden
+    _require_gpu(ref)
+    lib = _lib.load()
+    Bt, H, W = ref.shape[:3]
+    r0, r1 = (0, Bt) if rows is None else rows
+    if not 0 <= r0 < r1 <= Bt:
+        raise ValueError(f"freeu: rows {rows} outside the batch of {Bt}")
+    for t in (hidden, skip, out):
+        if t is not None and (t.dim() != 4 or tuple(t.shape[:3]) != (Bt, H, W) or t.dtype != ref.dtype or not t.is_contiguous()):
+            raise ValueError("freeu: hidden / skip / out are contiguous NHWC tensors of one dtype over one map")
+
+    def at(t):  # device address of sample r0
+        return None if t is None else t.data_ptr() + r0 * t.stride(0) * t.element_size()
+
+    hl, sl = lo_of(hidden), lo_of(skip)
+    ol = None
+    if skip is not None:
+        if out is None:
+            out = torch.empty_like(skip)
+        if out.shape != skip.shape:
+            raise ValueError("freeu: out has the shape of skip")
+        if sl is not None:
+            ol = sl if out is skip else lo_of(out)
+            if ol is None:
+                ol = torch.empty(out.shape, dtype=lo_dtype(out.dtype), device=out.device)
+            out.lo = ol
+        elif lo_of(out) is not None:
+            del out.lo
+    elif out is not None:
+        raise ValueError("freeu: out without a skip")
+    e0 = _prof_begin()
+    check(lib.ur_freeu(at(hidden), at(hl), hidden.shape[3] if hidden is not None else 0, float(b),
+                       at(skip), at(sl), at(out), at(ol), skip.shape[3] if skip is not None else 0, float(s),
+                       r1 - r0, H, W, DT[ref.dtype], _stream()), "ur_freeu")
+    nb = (hidden[r0:r1].numel() if hidden is not None else 0) + (2 * skip[r0:r1].numel() if skip is not None else 0)
+    _prof_end(e0, "freeu", 0.0, float(nb * ref.element_size()))
+    return out
+
+
 class _AddItem(C.Structure):
     _fields_ = [("a", C.c_void_p), ("a_lo", C.c_void_p), ("b", C.c_void_p), ("b_lo", C.c_void_p), ("out", C.c_void_p),
                 ("out_lo", C.c_void_p), ("n", C.c_int64)]

@@ -27,6 +27,7 @@ from .controlnet import AttributeDecoderModel, AttributeEncoderModel, UNet2DCond
 from . import ops
 from .graph import GraphedDualStreamStep, GraphedHoistedStep, dual_stream_step
 from .schedulers import DDIMScheduler, retrieve_timesteps
+from .unet_2d_blocks import freeu_state
 
 SCHEDULER_NAMES = ("img", "attr", "material", "albedo", "normal", "spec_light", "diff_light", "env")
 ATTR_GROUPS = ("material", "normal", "albedo", "spec_light", "diff_light", "env")  # after the mask group
@@ -87,6 +88,19 @@ class UniRendererPipeline:
         detected per sampling call through ``_weights_signature``."""
         self._graphs.clear()
         self._sample_graphs.clear()
+
+    def enable_freeu(self, s1: float, s2: float, b1: float, b2: float):
+        """FreeU (arXiv 2309.11497; ref 739-759) on the image stream's UNet: ``s1`` / ``s2`` attenuate the lowest frequencies of
+        the skips of up-block stage 1 / 2, ``b1`` / ``b2`` amplify the first half of their backbone channels.  The factors are
+        kernel arguments of the captured step, so they are part of the graph key (``_graph_for``): graphs captured in
+        another FreeU state are never replayed."""
+        if getattr(self, "unet", None) is None:
+            raise ValueError("The pipeline must have `unet` for using FreeU.")
+        self.unet.enable_freeu(s1=s1, s2=s2, b1=b1, b2=b2)
+
+    def disable_freeu(self):
+        """ref 762-764."""
+        self.unet.disable_freeu()
 
     def _weights_signature(self):
         """(device, (data_ptr, version) of every parameter) of the three networks: in-place updates bump ``_version``,
@@ -251,13 +265,19 @@ class UniRendererPipeline:
             rows.append(torch.stack([a_t.sqrt(), (1 - a_t).sqrt(), a_prev.sqrt(), (1 - a_prev).sqrt()]).float())
         return torch.stack(rows), torch.tensor(ts, dtype=torch.float32)
 
+    def _graph_key(self, x_img, ehs, run_decoder, cond_scale: float = 1.0):
+        """Everything a captured step bakes in besides the weights: shapes, dtype, executor, conditioning scale and the
+        UNet's FreeU factors (kernel arguments of ``ur_freeu``)."""
+        B, _, h, w = x_img.shape
+        return (str(x_img.device), B, h, w, ehs.shape[1], ehs.shape[2], run_decoder, self.unet.dtype, float(cond_scale),
+                self.hoist_invariants, self.rerun_invariants, freeu_state(self.unet))
+
     def _graph_for(self, x_img, cond28, ehs, run_decoder, cond_scale: float = 1.0, sig=None):
         """The captured step for these shapes / this conditioning scale, re-captured when the weights it baked in have
         changed since (``sig`` = a ``_weights_signature()`` the caller took once for its whole sampling call)."""
         B, _, h, w = x_img.shape
         dt = self.unet.dtype
-        key = (str(x_img.device), B, h, w, ehs.shape[1], ehs.shape[2], run_decoder, dt, float(cond_scale),
-               self.hoist_invariants, self.rerun_invariants)
+        key = self._graph_key(x_img, ehs, run_decoder, cond_scale)
         sig = sig if sig is not None else self._weights_signature()
         g = self._graphs.get(key)
         if g is not None and g.weights_sig != sig:  # stale packed weights: drop it and every sampling graph built on it

@@ -24,6 +24,7 @@ from . import backward as B
 from . import ops
 from .controlnet import CIN_PAD
 from .layers import BasicTransformerBlock, ResnetBlock2D
+from .unet_2d_blocks import freeu_enabled
 
 
 BATCH_CASTS = X.flag("batch_casts", True)
@@ -240,10 +241,16 @@ def _down_mid(net, x, temb_act, ehs, dt):
     return x, skips
 
 
+FREEU_AUTOGRAD_MSG = ("FreeU is enabled on this network's up blocks, but the differentiable path has no backward for it: FreeU is a "
+                      "sampling-time switch -- call disable_freeu() for training, or run the forward under torch.no_grad()")
+
+
 def _up_out(net, x, skips: List[torch.Tensor], temb_act, ehs, dt, extras=None, collect=None):
     """Up path + conv_out.  ``extras``: per-resnet tensors added after each resnet(/transformer) of an ``UpRes*`` block
     (unet_2d_blocks.py:2408, 2814); ``collect``: list that receives the per-layer outputs (the reference-modified
     blocks return them, 2584-2590 / 2697-2704)."""
+    if freeu_enabled(net):
+        raise NotImplementedError(FREEU_AUTOGRAD_MSG)
     temb = _temb_projections(_resnets_of(net.up_blocks), temb_act, dt)
     ehs = _context_projections(net.up_blocks, ehs, dt)
     skips = list(skips)

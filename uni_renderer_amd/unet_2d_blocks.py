@@ -106,6 +106,34 @@ class UNetMidBlock2DCrossAttn(nn.Module):
         return hidden_states
 
 
+FREEU_KEYS = ("s1", "s2", "b1", "b2")
+
+
+def freeu_params(block):
+    """``(b, s)`` of diffusers' ``apply_freeu`` for this up block, or None: FreeU (arXiv 2309.11497) is on when all four of
+    ``s1 s2 b1 b2`` (set by ``UNet2DConditionModel.enable_freeu``) are truthy (ref 2343-2348, 2522-2527), and acts on the
+    blocks with ``resolution_idx`` 0 (b1, s1) and 1 (b2, s2) only."""
+    s1, s2, b1, b2 = (getattr(block, k, None) for k in FREEU_KEYS)
+    if not (s1 and s2 and b1 and b2):
+        return None
+    idx = getattr(block, "resolution_idx", None)
+    if idx == 0:
+        return float(b1), float(s1)
+    if idx == 1:
+        return float(b2), float(s2)
+    return None
+
+
+def freeu_enabled(net) -> bool:
+    """True when an up block of ``net`` would apply FreeU."""
+    return any(freeu_params(blk) is not None for blk in getattr(net, "up_blocks", ()))
+
+
+def freeu_state(net):
+    """The FreeU factors of every up block of ``net`` (None where it is off): what a captured graph of ``net`` bakes in."""
+    return tuple(freeu_params(blk) for blk in getattr(net, "up_blocks", ()))
+
+
 def _up_resnets(in_channels, out_channels, prev_output_channel, temb_channels, num_layers, groups, eps, osf):
     rs = []
     for i in range(num_layers):
@@ -135,9 +163,12 @@ class UpBlock2D(nn.Module):
     def forward(self, hidden_states, res_hidden_states_tuple, ctx: Ctx, upsample_size=None,
                 up_additional_states_tuple=None):
         output_states = ()
+        fu = freeu_params(self)
         for k, resnet in enumerate(self.resnets):
             res = res_hidden_states_tuple[-1]
             res_hidden_states_tuple = res_hidden_states_tuple[:-1]
+            if fu is not None:  # ref 2653-2677: hidden is scaled in place (the caller's tensor too), the skip is a new tensor
+                res = ops.freeu(hidden_states, res, *fu)
             hidden_states = resnet(hidden_states, ctx, x1=res)
             if self.adds_up_states and up_additional_states_tuple is not None:  # UpResBlock2D (ref 2814)
                 hidden_states = ops.add(hidden_states, up_additional_states_tuple[k])
@@ -176,9 +207,12 @@ class CrossAttnUpBlock2D(nn.Module):
     def forward(self, hidden_states, res_hidden_states_tuple, ctx: Ctx, upsample_size=None,
                 up_additional_states_tuple=None):
         output_states = ()
+        fu = freeu_params(self)
         for k, (resnet, attn) in enumerate(zip(self.resnets, self.attentions)):
             res = res_hidden_states_tuple[-1]
             res_hidden_states_tuple = res_hidden_states_tuple[:-1]
+            if fu is not None:  # ref 2522-2546
+                res = ops.freeu(hidden_states, res, *fu)
             hidden_states = attn(resnet(hidden_states, ctx, x1=res), ctx)
             if self.adds_up_states and up_additional_states_tuple is not None:  # CrossAttnUpResBlock2D (ref 2408)
                 hidden_states = ops.add(hidden_states, up_additional_states_tuple[k])
