@@ -46,7 +46,7 @@
 extern "C" {
 #endif
 
-#define UR_ABI_VERSION 14
+#define UR_ABI_VERSION 15
 
 #define UR_E_BADARG (-1001)   /* inconsistent descriptor (shape / alignment / null pointer)   */
 #define UR_E_UNSUPPORTED (-1002) /* shape outside what the kernels are instantiated for       */
@@ -59,7 +59,9 @@ extern "C" {
 #define UR_ACT_SILU 1
 #define UR_ACT_GEGLU 2
 
-/* Tile configurations of ur_igemm (rows x cols of the output tile computed by one workgroup). */
+/* Tile configurations of ur_igemm (rows x cols of the output tile computed by one workgroup).  These numbers are stored in
+ * the tuning tables; what each id builds is ONE row of csrc/igemm_tiles.h (a new build: a #define here, a row there,
+ * UR_TILE_COUNT + 1), readable at run time through ur_igemm_tile_info. */
 #define UR_TILE_AUTO 0
 #define UR_TILE_128x128 1
 #define UR_TILE_128x64 2      /* 3-deep LDS ring */
@@ -245,6 +247,19 @@ int ur_igemm_splitk_gn(const ur_igemm_desc* d, const float* gamma, const float* 
  * product build returns 0 and UR_E_UNSUPPORTED for those tile ids. */
 int ur_has_wsconv(void);
 int ur_has_pp(void);     /* 1: the ping-pong tiles (UR_TILE_PP_*) are built in (`make PP=1`); else they return UR_E_UNSUPPORTED */
+
+/* One row of the tile table (csrc/igemm_tiles.h), host only (ABI 15): the output tile, the kernel family, whether THIS
+ * library can launch the id (0: the reserved id, and the WS / PP families without `make WSCONV=1` / `make PP=1`) and the
+ * short label the Python host puts into its profile keys.  0, or UR_E_BADARG for an id outside [1, UR_TILE_COUNT). */
+#define UR_TILE_FAMILY_LOCKSTEP 0 /* igemm_kernel (csrc/igemm.hip) */
+#define UR_TILE_FAMILY_WS 1       /* weight-streaming conv (csrc/wsconv.hip) */
+#define UR_TILE_FAMILY_PP 2       /* 8-wave ping-pong (csrc/igemm_pp.hip) */
+#define UR_TILE_FAMILY_RESERVED 3 /* id kept, nothing instantiated */
+typedef struct ur_tile_info {
+    int32_t bm, bn, family, built;
+    char label[16];
+} ur_tile_info;
+int ur_igemm_tile_info(int tile, ur_tile_info* out);
 
 /* Workspace (in floats) ur_igemm needs in `partial` for this descriptor (0 when splitk <= 1). */
 int64_t ur_igemm_partial_floats(const ur_igemm_desc* d);
@@ -747,6 +762,7 @@ int ur_abi_version(void);
 const char* ur_build_info(void);
 /* sizeof() of the descriptor structs as compiled, so a binding can verify its mirror of the layout. */
 int ur_sizeof_igemm_desc(void);
+int ur_sizeof_tile_info(void);
 int ur_sizeof_attn_desc(void);
 int ur_sizeof_attn_bwd_desc(void);
 int ur_sizeof_tchain_desc(void);

@@ -42,6 +42,37 @@ def test_bad_descriptor_is_rejected_without_gpu():
     assert lib.ur_add(None, None, 1.0, None, 8, 0, None) == -1001
 
 
+def test_tile_table_answers_for_every_id_and_matches_the_test_lists():
+    """ur_igemm_tile_info is the one description of the tile builds (csrc/igemm_tiles.h): every id answers, the opt-in families
+    say whether they are built in, and the literal tile lists the GPU tests are parametrised by are its families."""
+    import test_ops_gpu as T
+    from uni_renderer_amd import _lib, ops
+
+    lib = _lib.load()
+    header = open(os.path.join(ROOT, "include", "ur_kernels.h")).read()
+    count = int(re.search(r"#define UR_TILE_COUNT (\d+)", header).group(1))
+    assert count == 62
+    info = ops.TileInfo()
+    for bad in (0, count, -1):
+        assert lib.ur_igemm_tile_info(bad, ctypes.byref(info)) == -1001  # UR_E_BADARG
+    assert lib.ur_igemm_tile_info(1, None) == -1001
+    family = {}
+    for tile in range(1, count):
+        assert lib.ur_igemm_tile_info(tile, ctypes.byref(info)) == 0, tile
+        assert info.bm > 0 and info.bn > 0 and info.bm % 64 == 0 and info.bn % 32 == 0 and info.label, tile
+        built = {ops.TILE_FAMILY_LOCKSTEP: 1, ops.TILE_FAMILY_WS: lib.ur_has_wsconv(), ops.TILE_FAMILY_PP: lib.ur_has_pp(),
+                 ops.TILE_FAMILY_RESERVED: 0}[info.family]
+        assert info.built == built, tile
+        family.setdefault(info.family, []).append(tile)
+    assert family[ops.TILE_FAMILY_RESERVED] == [39]
+    assert family[ops.TILE_FAMILY_WS] == [ops.TILE_WS320, ops.TILE_WS320_W8]
+    assert T.PP_TILES == family[ops.TILE_FAMILY_PP]
+    assert sorted(T.ALL_TILES) == sorted(family[ops.TILE_FAMILY_LOCKSTEP] + family[ops.TILE_FAMILY_PP])
+    assert len(set(T.ALL_TILES)) == len(T.ALL_TILES)
+    assert set(T.DXS_TILES) <= set(family[ops.TILE_FAMILY_LOCKSTEP])
+    assert list(ops.tile_table()) == [t for t in range(1, count) if t != 39]  # what the tuning tools iterate
+
+
 def test_no_cpu_fallback_and_loud_failure():
     from uni_renderer_amd import ops
 
@@ -169,7 +200,7 @@ def test_plan_igemm_is_sane():
     for (M, N, K, taps) in [(16384, 320, 2880, 9), (4096, 640, 5760, 9), (256, 1280, 23040, 9), (4, 1280, 320, 1),
                             (308, 320, 768, 1), (16384, 2560, 320, 1)]:
         tile, sk = ops.plan_igemm(M, N, K, taps)
-        assert tile in ops._TILES and sk in (1, 2, 4, 8, 16) and (sk == 1 or K // 64 >= 4 * sk)  # (a measured-table row or the planner)
+        assert tile in ops.tile_table() and sk in (1, 2, 4, 8, 16) and (sk == 1 or K // 64 >= 4 * sk)  # (a measured-table row or the planner)
     assert ops.plan_igemm(256, 1280, 23040, 9)[1] > 1  # tiny-M, huge-K layers must split K to fill 256 CUs
 
 

@@ -92,7 +92,7 @@ def main():
         fl = 2.0 * M * N * K * S
         if args.sweep:
             res = {}
-            for tile in ([int(t) for t in args.tiles.split(",")] if args.tiles else ops._TILES):
+            for tile in ([int(t) for t in args.tiles.split(",")] if args.tiles else ops.tile_table()):
                 for sk in (1, 2, 4, 8, 16):
                     if sk > 1 and K // 64 < 4 * sk:
                         continue

@@ -68,7 +68,7 @@ def main():
     lib = _lib.load()
     models = bench.build_models(dev, torch.float16)
     calls = tune_igemm.collect(models, bench.make_inputs(args.batch, args.latent, dev, torch.float16, seed=7), grouped=True)
-    tiles = [int(t) for t in args.tiles.split(",")] if args.tiles else list(ops._TILES)
+    tiles = [int(t) for t in args.tiles.split(",")] if args.tiles else list(ops.tile_table())
     sks = [int(s) for s in args.splitk.split(",")]
     pf_stream = torch.cuda.Stream()
     report = []

@@ -48,7 +48,7 @@ def main():
         ref = out.float().clone()
         res = {}
         for tile in tiles:
-            bm, bn = ops._TILES[tile][:2]
+            bm, bn = ops.tile_table()[tile][:2]
             for sk in (1, 2, 4, 8):
                 if sk > 1 and K // 64 < 4 * sk:
                     continue

@@ -184,7 +184,7 @@ def main():
         global _scrub
         _scrub = (torch.zeros(24 << 20, dtype=torch.float16, device=dev), torch.zeros(24 << 20, dtype=torch.float16, device=dev))
     models = None if args.train else bench.build_models(dev, dtype)
-    tiles = [int(t) for t in args.tiles.split(",")] if args.tiles else list(ops._TILES)
+    tiles = [int(t) for t in args.tiles.split(",")] if args.tiles else list(ops.tile_table())
     shapes = [(args.batch, args.latent)] + [tuple(int(v) for v in p.split(",")) for p in args.also.split(";") if p]
     ops.load_tuning_table("/nonexistent")  # start from the analytic planner
     table, report = {}, []

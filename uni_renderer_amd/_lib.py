@@ -14,7 +14,7 @@ import torch  # noqa: F401  (must be imported first, see module docstring)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("UR_LIB_PATH", os.path.join(_HERE, "liburhip.so"))  # override = kernel experiments only
-ABI_VERSION = 14
+ABI_VERSION = 15
 
 i32, i64, f32, vp = C.c_int32, C.c_int64, C.c_float, C.c_void_p
 
@@ -90,6 +90,8 @@ class TChainDesc(C.Structure):
 SYMBOLS = {
     "ur_igemm": (C.c_int, [C.POINTER(IGemmDesc), vp]),
     "ur_igemm_partial_floats": (C.c_int64, [C.POINTER(IGemmDesc)]),
+    "ur_igemm_tile_info": (C.c_int, [C.c_int, vp]),
+    "ur_sizeof_tile_info": (C.c_int, []),
     "ur_groupnorm_stats": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp]),
     "ur_groupnorm_apply": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp,
                                      vp, C.c_float, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp]),

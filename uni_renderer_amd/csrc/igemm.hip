@@ -18,8 +18,10 @@
 //     permuted while loading so that those channels are 16 consecutive ones -> 32-byte vector
 //     stores/loads per lane and full 128-byte lines per pixel row in the epilogue.
 #include <cstdlib>
+#include <cstring>
 
 #include "igemm_epi.h"
+#include "igemm_tiles.h"
 
 namespace ur {
 
@@ -658,29 +660,7 @@ __global__ void __launch_bounds__(RGN_THREADS) igemm_splitk_reduce_gn(const ur_i
 // ---------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------
-struct TileCfg { int bm, bn, stages; };
-// index = UR_TILE_* (include/ur_kernels.h)
-static const TileCfg kTiles[UR_TILE_COUNT] = {{0, 0, 0},      {128, 128, 2}, {128, 64, 3}, {64, 64, 3},
-                                              {128, 128, 3}, {128, 64, 2},  {64, 64, 4},  {64, 64, 2},
-                                              {256, 128, 2}, {128, 320, 2}, {128, 256, 2}, {256, 256, 2},
-                                              {64, 64, -2},  {128, 64, -2}, {128, 128, -2}, {128, 320, -2},
-                                              {256, 128, -2}, {64, 64, 2},   {128, 64, 2},   {64, 64, 3},
-                                              {64, 128, 2},  {64, 64, 4},
-                                              // 32x32x16-MFMA builds (UR_TILE_*_M32)
-                                              {128, 320, 2}, {128, 128, 2}, {128, 64, 2}, {128, 64, 3}, {64, 64, 2},
-                                              {64, 64, 3},   {256, 256, 2}, {256, 128, 2}, {128, 256, 2},
-                                              // wave-specialised builds: dedicated loader waves (UR_TILE_*_L<n>)
-                                              {128, 320, 2}, {128, 320, 2}, {128, 128, 2}, {128, 128, 3}, {128, 64, 2},
-                                              {128, 64, 3},  {64, 64, 3},   {256, 128, 2}, {256, 256, 2}, {128, 256, 2},
-                                              {128, 256, 3}, {128, 320, 2}, {256, 320, 2}, {128, 160, 2},
-                                              {128, 160, 3}, {64, 320, 2},
-                                              // weight-streaming conv (wsconv.hip): 4 and 8 waves
-                                              {128, 320, 2}, {128, 320, 2},
-                                              // 8-wave ping-pong builds (igemm_pp.hip)
-                                              {128, 320, 5}, {128, 320, 4}, {256, 128, 5}, {128, 256, 5}, {256, 256, 4},
-                                              {128, 128, 5}, {256, 320, 4},
-                                              // round 6: few waves, big per-wave tiles (UR_TILE_*_W4_M32 / _W8_M32)
-                                              {256, 160, 2}, {256, 320, 2}, {128, 320, 2}, {256, 128, 2}, {256, 256, 2}, {256, 320, 2}};
+// kTiles[UR_TILE_*] = {bm, bn, family, label}: igemm_tiles.h, generated from its one list of tile builds
 
 static int pick_tile(const ur_igemm_desc& d) {
     // Cost model: the busiest CU runs ceil(workgroups / 256) tiles; bigger tiles have a better
@@ -704,7 +684,19 @@ static void ensure_lds_limit(int lds) {
     set_lds_limit_once(done, reinterpret_cast<const void*>(&igemm_kernel<T, BM, BN, WM, WN, NSTAGE, CONV, MF, NL>), lds);
 }
 
-template <typename T, int BM, int BN, int WM, int WN, int NSTAGE, int MF = 16, int NL = 0>
+// the split-K second pass over the fp32 slabs of `d` (igemm_splitk_reduce), shared by every main-pass kernel
+template <typename T>
+static int launch_splitk_reduce(const ur_igemm_desc& d, hipStream_t s) {
+    const int64_t total = (int64_t)d.M * (d.ldp / 16);
+    int blocks = (int)((total + 255) / 256);
+    if (blocks > 4096) blocks = 4096;
+    if (total * d.zbatch < REDUCE_PIPE_MAX_THREADS) hipLaunchKernelGGL((igemm_splitk_reduce<T, true>), dim3(blocks, d.zbatch), dim3(256), 0, s, d);
+    else hipLaunchKernelGGL((igemm_splitk_reduce<T, false>), dim3(blocks, d.zbatch), dim3(256), 0, s, d);
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? 0 : -(int)e;
+}
+
+template <typename T, int BM, int BN, int WM, int WN, int NSTAGE, int MF, int NL>
 static int launch_cfg(const ur_igemm_desc& d, hipStream_t s, bool reduce) {
     const int tiles_m = (d.M + BM - 1) / BM, tiles_n = (d.N + BN - 1) / BN;
     dim3 grid(tiles_m * tiles_n, 1, d.zbatch * d.splitk);
@@ -719,15 +711,7 @@ static int launch_cfg(const ur_igemm_desc& d, hipStream_t s, bool reduce) {
     }
     e = hipGetLastError();
     if (e != hipSuccess) return -(int)e;
-    if (d.splitk > 1) {
-        const int64_t total = (int64_t)d.M * (d.ldp / 16);
-        int blocks = (int)((total + 255) / 256);
-        if (blocks > 4096) blocks = 4096;
-        if (total * d.zbatch < REDUCE_PIPE_MAX_THREADS) hipLaunchKernelGGL((igemm_splitk_reduce<T, true>), dim3(blocks, d.zbatch), dim3(256), 0, s, d);
-        else hipLaunchKernelGGL((igemm_splitk_reduce<T, false>), dim3(blocks, d.zbatch), dim3(256), 0, s, d);
-        e = hipGetLastError();
-        if (e != hipSuccess) return -(int)e;
-    }
+    if (d.splitk > 1 && reduce) return launch_splitk_reduce<T>(d, s);
     return 0;
 }
 
@@ -763,15 +747,7 @@ template <typename T>
 static int launch_pp(const ur_igemm_desc& d, hipStream_t s, bool reduce) {
     const int rc = igemm_pp_launch(d, s);
     if (rc) return rc;
-    if (d.splitk > 1 && reduce) {
-        const int64_t total = (int64_t)d.M * (d.ldp / 16);
-        int blocks = (int)((total + 255) / 256);
-        if (blocks > 4096) blocks = 4096;
-        if (total * d.zbatch < REDUCE_PIPE_MAX_THREADS) hipLaunchKernelGGL((igemm_splitk_reduce<T, true>), dim3(blocks, d.zbatch), dim3(256), 0, s, d);
-        else hipLaunchKernelGGL((igemm_splitk_reduce<T, false>), dim3(blocks, d.zbatch), dim3(256), 0, s, d);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return -(int)e;
-    }
+    if (d.splitk > 1 && reduce) return launch_splitk_reduce<T>(d, s);
     return 0;
 }
 
@@ -780,15 +756,7 @@ template <typename T>
 static int launch_ws(const ur_igemm_desc& d, hipStream_t s, bool reduce) {
     const int rc = wsconv_launch(d, s);
     if (rc) return rc;
-    if (d.splitk > 1 && reduce) {
-        const int64_t total = (int64_t)d.M * (d.ldp / 16);
-        int blocks = (int)((total + 255) / 256);
-        if (blocks > 4096) blocks = 4096;
-        if (total * d.zbatch < REDUCE_PIPE_MAX_THREADS) hipLaunchKernelGGL((igemm_splitk_reduce<T, true>), dim3(blocks, d.zbatch), dim3(256), 0, s, d);
-        else hipLaunchKernelGGL((igemm_splitk_reduce<T, false>), dim3(blocks, d.zbatch), dim3(256), 0, s, d);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return -(int)e;
-    }
+    if (d.splitk > 1 && reduce) return launch_splitk_reduce<T>(d, s);
     return 0;
 }
 
@@ -800,71 +768,18 @@ static int launch_dtype(ur_igemm_desc& d, hipStream_t s, bool reduce) {
         if (bm && igemm_dxs_ok(d, bm)) {
             const int rc = igemm_dxs_launch(d, s);
             if (rc) return rc;
-            if (d.splitk > 1 && reduce) {
-                const int64_t total = (int64_t)d.M * (d.ldp / 16);
-                int blocks = (int)((total + 255) / 256);
-                if (blocks > 4096) blocks = 4096;
-                if (total * d.zbatch < REDUCE_PIPE_MAX_THREADS) hipLaunchKernelGGL((igemm_splitk_reduce<T, true>), dim3(blocks, d.zbatch), dim3(256), 0, s, d);
-        else hipLaunchKernelGGL((igemm_splitk_reduce<T, false>), dim3(blocks, d.zbatch), dim3(256), 0, s, d);
-                const hipError_t e = hipGetLastError();
-                if (e != hipSuccess) return -(int)e;
-            }
+            if (d.splitk > 1 && reduce) return launch_splitk_reduce<T>(d, s);
             return 0;
         }
     }
     switch (d.tile) {
-        case UR_TILE_128x128: return launch_cfg<T, 128, 128, 2, 2, 2>(d, s, reduce);
-        case UR_TILE_128x64: return launch_cfg<T, 128, 64, 4, 1, 3>(d, s, reduce);
-        case UR_TILE_64x64: return launch_cfg<T, 64, 64, 4, 1, 3>(d, s, reduce);
-        case UR_TILE_128x128_S3: return launch_cfg<T, 128, 128, 2, 2, 3>(d, s, reduce);
-        case UR_TILE_128x64_S2: return launch_cfg<T, 128, 64, 4, 1, 2>(d, s, reduce);
-        case UR_TILE_64x64_S4: return launch_cfg<T, 64, 64, 4, 1, 4>(d, s, reduce);
-        case UR_TILE_64x64_S2: return launch_cfg<T, 64, 64, 4, 1, 2>(d, s, reduce);
-        case UR_TILE_256x128: return launch_cfg<T, 256, 128, 4, 2, 2>(d, s, reduce);
-        case UR_TILE_128x320: return launch_cfg<T, 128, 320, 2, 5, 2>(d, s, reduce);
-        case UR_TILE_128x256: return launch_cfg<T, 128, 256, 2, 4, 2>(d, s, reduce);
-        case UR_TILE_256x256: return launch_cfg<T, 256, 256, 4, 4, 2>(d, s, reduce);
-        case UR_TILE_64x64_R: return launch_cfg<T, 64, 64, 4, 1, -2>(d, s, reduce);
-        case UR_TILE_128x64_R: return launch_cfg<T, 128, 64, 4, 1, -2>(d, s, reduce);
-        case UR_TILE_128x128_R: return launch_cfg<T, 128, 128, 2, 2, -2>(d, s, reduce);
-        case UR_TILE_128x320_R: return launch_cfg<T, 128, 320, 2, 5, -2>(d, s, reduce);
-        case UR_TILE_256x128_R: return launch_cfg<T, 256, 128, 4, 2, -2>(d, s, reduce);
-        case UR_TILE_64x64_W1: return launch_cfg<T, 64, 64, 1, 1, 2>(d, s, reduce);
-        case UR_TILE_128x64_W2: return launch_cfg<T, 128, 64, 2, 1, 2>(d, s, reduce);
-        case UR_TILE_64x64_W1_S3: return launch_cfg<T, 64, 64, 1, 1, 3>(d, s, reduce);
-        case UR_TILE_64x128_W2: return launch_cfg<T, 64, 128, 1, 2, 2>(d, s, reduce);
-        case UR_TILE_64x64_W1_S4: return launch_cfg<T, 64, 64, 1, 1, 4>(d, s, reduce);
-        case UR_TILE_128x320_M32: return launch_cfg<T, 128, 320, 2, 5, 2, 32>(d, s, reduce);
-        case UR_TILE_128x128_M32: return launch_cfg<T, 128, 128, 2, 2, 2, 32>(d, s, reduce);
-        case UR_TILE_128x64_M32: return launch_cfg<T, 128, 64, 4, 1, 2, 32>(d, s, reduce);
-        case UR_TILE_128x64_S3_M32: return launch_cfg<T, 128, 64, 4, 1, 3, 32>(d, s, reduce);
-        case UR_TILE_64x64_M32: return launch_cfg<T, 64, 64, 2, 2, 2, 32>(d, s, reduce);
-        case UR_TILE_64x64_S3_M32: return launch_cfg<T, 64, 64, 2, 2, 3, 32>(d, s, reduce);
-        case UR_TILE_256x256_M32: return launch_cfg<T, 256, 256, 4, 4, 2, 32>(d, s, reduce);
-        case UR_TILE_256x128_M32: return launch_cfg<T, 256, 128, 4, 2, 2, 32>(d, s, reduce);
-        case UR_TILE_128x256_M32: return launch_cfg<T, 128, 256, 2, 4, 2, 32>(d, s, reduce);
-        case UR_TILE_128x320_L2: return launch_cfg<T, 128, 320, 2, 5, 2, 16, 2>(d, s, reduce);
-        case UR_TILE_128x320_L4: return launch_cfg<T, 128, 320, 2, 5, 2, 16, 4>(d, s, reduce);
-        case UR_TILE_128x128_L2: return launch_cfg<T, 128, 128, 2, 2, 2, 16, 2>(d, s, reduce);
-        case UR_TILE_128x128_S3_L2: return launch_cfg<T, 128, 128, 2, 2, 3, 16, 2>(d, s, reduce);
-        case UR_TILE_128x64_L1: return launch_cfg<T, 128, 64, 4, 1, 2, 16, 1>(d, s, reduce);
-        case UR_TILE_128x64_S3_L2: return launch_cfg<T, 128, 64, 4, 1, 3, 16, 2>(d, s, reduce);
-        case UR_TILE_64x64_S3_L1: return launch_cfg<T, 64, 64, 4, 1, 3, 16, 1>(d, s, reduce);
-        case UR_TILE_256x128_L2: return launch_cfg<T, 256, 128, 4, 2, 2, 16, 2>(d, s, reduce);
-        case UR_TILE_256x256_L0: return UR_E_UNSUPPORTED;  /* 16 consumer waves already fill the 1024-thread limit */
-        case UR_TILE_128x256_L2: return launch_cfg<T, 128, 256, 2, 4, 2, 16, 2>(d, s, reduce);
-        case UR_TILE_128x256_S3: return launch_cfg<T, 128, 256, 2, 4, 3>(d, s, reduce);
-        case UR_TILE_128x320_W8_M32: return launch_cfg<T, 128, 320, 4, 2, 2, 32>(d, s, reduce);
-        case UR_TILE_256x320_W16_M32: return launch_cfg<T, 256, 320, 8, 2, 2, 32>(d, s, reduce);
-        case UR_TILE_128x160_M32: return launch_cfg<T, 128, 160, 4, 1, 2, 32>(d, s, reduce);
-        case UR_TILE_128x160_S3_M32: return launch_cfg<T, 128, 160, 4, 1, 3, 32>(d, s, reduce);
-        case UR_TILE_64x320_M32: return launch_cfg<T, 64, 320, 2, 2, 2, 32>(d, s, reduce);
-        case UR_TILE_256x160_W4_M32: return launch_cfg<T, 256, 160, 4, 1, 2, 32>(d, s, reduce);
-        case UR_TILE_256x320_W8_M32: return launch_cfg<T, 256, 320, 4, 2, 2, 32>(d, s, reduce);
-        case UR_TILE_128x320_W4_M32: return launch_cfg<T, 128, 320, 2, 2, 2, 32>(d, s, reduce);
-        case UR_TILE_256x128_W4_M32: return launch_cfg<T, 256, 128, 4, 1, 2, 32>(d, s, reduce);
-        case UR_TILE_256x256_W8_M32: return launch_cfg<T, 256, 256, 4, 2, 2, 32>(d, s, reduce);
-        case UR_TILE_256x320_W10: return launch_cfg<T, 256, 320, 2, 5, 2>(d, s, reduce);
+#define UR_TILE_CASE_LS(id, BM, BN, WM, WN, NSTAGE, MF, NL, label) \
+    case id: return launch_cfg<T, BM, BN, WM, WN, NSTAGE, MF, NL>(d, s, reduce);
+#define UR_TILE_CASE_EXT(id, family, BM, BN, label)
+        UR_IGEMM_TILES(UR_TILE_CASE_LS, UR_TILE_CASE_EXT)
+#undef UR_TILE_CASE_LS
+#undef UR_TILE_CASE_EXT
+        case UR_TILE_256x256_L0: return UR_E_UNSUPPORTED;  /* reserved */
         case UR_TILE_WS320: return launch_ws<T>(d, s, reduce);
         case UR_TILE_WS320_W8: return launch_ws<T>(d, s, reduce);
         case UR_TILE_PP_128x320: case UR_TILE_PP_128x320_S4: case UR_TILE_PP_256x128: case UR_TILE_PP_128x256:
@@ -894,6 +809,18 @@ extern "C" int ur_has_wsconv(void) {
 #else
     return 0;
 #endif
+}
+
+extern "C" int ur_sizeof_tile_info(void) { return (int)sizeof(ur_tile_info); }
+
+extern "C" int ur_igemm_tile_info(int tile, ur_tile_info* out) {
+    if (!out || tile < 1 || tile >= UR_TILE_COUNT) return UR_E_BADARG;
+    const ur::TileCfg& t = ur::kTiles[tile];
+    const int built = t.family == UR_TILE_FAMILY_LOCKSTEP ? 1 : t.family == UR_TILE_FAMILY_WS ? ur_has_wsconv() : t.family == UR_TILE_FAMILY_PP ? ur_has_pp() : 0;
+    *out = ur_tile_info{t.bm, t.bn, t.family, built, {0}};
+    static_assert(sizeof(out->label) == sizeof(t.label), "ur_tile_info.label vs igemm_tiles.h");
+    std::memcpy(out->label, t.label, sizeof(out->label));
+    return 0;
 }
 
 extern "C" int64_t ur_igemm_partial_floats(const ur_igemm_desc* d) {

@@ -20,6 +20,7 @@
 // Eligible: taps == 9, stride 1, pad 1, one source, W_out a power of two >= 8 dividing the tile height BM (all resnet convs of
 // the UNets at 64x64 .. 8x8, including the nearest-2x fused upsample convs); everything else stays on igemm.hip.
 #include "igemm_epi.h"
+#include "igemm_tiles.h"
 
 // -DUR_DXS_ABLATE=<bits>: timing-only builds (results are garbage; tools/experiments/r04_run13.sh):
 //   1 = the pixel block is never copied, 2 = fragment reads at the unshifted rows (address math hoisted out of the loop),
@@ -368,9 +369,9 @@ static int dxs_launch_dtype(const ur_igemm_desc& d, hipStream_t s) {
 // tile height of the tiles this file instantiates (0: none)
 int igemm_dxs_tile_bm(int tile) {
     switch (tile) {
-        case UR_TILE_128x320: case UR_TILE_128x64_S2: case UR_TILE_128x64: case UR_TILE_128x128: case UR_TILE_128x128_S3: return 128;
-        case UR_TILE_64x64_S2: case UR_TILE_64x64: case UR_TILE_64x64_S4: return 64;
-        case UR_TILE_256x128: return 256;
+        case UR_TILE_128x320: case UR_TILE_128x64_S2: case UR_TILE_128x64: case UR_TILE_128x128: case UR_TILE_128x128_S3:
+        case UR_TILE_64x64_S2: case UR_TILE_64x64: case UR_TILE_64x64_S4:
+        case UR_TILE_256x128: return kTiles[tile].bm;
     }
     return 0;
 }

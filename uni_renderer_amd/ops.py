@@ -21,39 +21,38 @@ DT_ANY = {torch.float16: 0, torch.bfloat16: 1, torch.float32: 2}
 ACT_NONE, ACT_SILU, ACT_GEGLU = 0, 1, 2
 TILE_AUTO, TILE_128x128, TILE_128x64, TILE_64x64 = 0, 1, 2, 3
 TILE_128x128_S3, TILE_128x64_S2, TILE_64x64_S4, TILE_64x64_S2 = 4, 5, 6, 7
-# tile id -> (BM, BN, relative efficiency guess for the analytic planner, LDS ring depth)
-_TILES = {TILE_128x128: (128, 128, 1.0, 2), TILE_128x64: (128, 64, 0.85, 3), TILE_64x64: (64, 64, 0.6, 3),
-          TILE_128x128_S3: (128, 128, 0.9, 3), TILE_128x64_S2: (128, 64, 0.7, 2), TILE_64x64_S4: (64, 64, 0.6, 4),
-          TILE_64x64_S2: (64, 64, 0.5, 2), 8: (256, 128, 1.1, 2), 9: (128, 320, 1.1, 2), 10: (128, 256, 1.1, 2),
-          11: (256, 256, 1.2, 2),
-          # register-staged loader variants (global_load -> VGPR -> ds_write), "stages" = "r"
-          12: (64, 64, 0.6, "r"), 13: (128, 64, 0.85, "r"), 14: (128, 128, 1.0, "r"), 15: (128, 320, 1.1, "r"),
-          16: (256, 128, 1.1, "r"),
-          # few-wave workgroups: every wave owns a full 64x64 tile (0.5 KB of LDS reads per MFMA instead of 1.25)
-          17: (64, 64, 0.8, "2w1"), 18: (128, 64, 0.9, "2w2"), 19: (64, 64, 0.8, "3w1"), 20: (64, 128, 0.9, "2w2n"),
-          21: (64, 64, 0.8, "4w1"),
-          # the same tiles on the 32x32x16 MFMA (UR_TILE_*_M32)
-          22: (128, 320, 1.2, "2m32"), 23: (128, 128, 1.1, "2m32"), 24: (128, 64, 0.9, "2m32"), 25: (128, 64, 0.9, "3m32"),
-          26: (64, 64, 0.7, "2m32"), 27: (64, 64, 0.7, "3m32"), 28: (256, 256, 1.3, "2m32"), 29: (256, 128, 1.2, "2m32"),
-          30: (128, 256, 1.2, "2m32"),
-          # wave-specialised builds: n dedicated loader waves (UR_TILE_*_L<n>); 39 is reserved / not instantiated
-          31: (128, 320, 1.3, "2L2"), 32: (128, 320, 1.3, "2L4"), 33: (128, 128, 1.2, "2L2"), 34: (128, 128, 1.2, "3L2"),
-          35: (128, 64, 1.0, "2L1"), 36: (128, 64, 1.0, "3L2"), 37: (64, 64, 0.8, "3L1"), 38: (256, 128, 1.3, "2L2"),
-          40: (128, 256, 1.3, "2L2"), 41: (128, 256, 1.2, 3), 42: (128, 320, 1.2, "2w8m32"), 43: (256, 320, 1.2, "2w16m32"), 44: (128, 160, 1.0, "2m32"), 45: (128, 160, 1.0, "3m32"),
-          46: (64, 320, 0.9, "2m32"),
-          # weight-streaming conv (csrc/wsconv.hip): ``w`` is the stage-image stream of wsconv_images()
-          47: (128, 320, 1.4, "ws"), 48: (128, 320, 1.4, "ws8"),
-          # 8-wave ping-pong builds (csrc/igemm_pp.hip): "pp<ring slots>"
-          49: (128, 320, 1.5, "pp5"), 50: (128, 320, 1.5, "pp4"), 51: (256, 128, 1.4, "pp5"), 52: (128, 256, 1.4, "pp5"),
-          53: (256, 256, 1.5, "pp4"), 54: (128, 128, 1.2, "pp5"), 55: (256, 320, 1.5, "pp4"),
-          # round 6: few waves with big per-wave tiles (64 x 160 / 64 x 128 per wave, one or two waves per SIMD)
-          56: (256, 160, 1.3, "2w4m32"), 57: (256, 320, 1.4, "2w8m32"), 58: (128, 320, 1.3, "2w4m32"), 59: (256, 128, 1.2, "2w4m32"),
-          60: (256, 256, 1.4, "2w8m32"), 61: (256, 320, 1.4, "2w10")}
 TILE_PP_128x320, TILE_PP_128x320_S4, TILE_PP_256x128, TILE_PP_128x256, TILE_PP_256x256, TILE_PP_128x128, TILE_PP_256x320 = range(49, 56)
 TILE_WS320, TILE_WS320_W8 = 47, 48
 # which build ``conv3x3(ws=...)`` launches: 8 waves per workgroup (two instruction streams per SIMD) or 4 (one)
 WSCONV_TILE = TILE_WS320_W8 if X.number("wsconv_waves", 8) == 8 else TILE_WS320
-_PLANNER_TILES = (TILE_128x128, TILE_128x64, TILE_64x64)
+# the analytic planner's candidates (plan_igemm, no measured row): tile id -> relative efficiency guess
+_PLANNER_TILES = {TILE_128x128: 1.0, TILE_128x64: 0.85, TILE_64x64: 0.6}
+TILE_FAMILY_LOCKSTEP, TILE_FAMILY_WS, TILE_FAMILY_PP, TILE_FAMILY_RESERVED = 0, 1, 2, 3  # UR_TILE_FAMILY_*
+
+
+class TileInfo(C.Structure):
+    """Mirror of ``ur_tile_info``: one row of the library's table of tile builds (csrc/igemm_tiles.h)."""
+
+    _fields_ = [("bm", C.c_int32), ("bn", C.c_int32), ("family", C.c_int32), ("built", C.c_int32), ("label", C.c_char * 16)]
+
+
+_lib.register_layout("ur_sizeof_tile_info", TileInfo)
+_tile_table = None
+
+
+def tile_table() -> dict:
+    """``{tile id: (BM, BN, label)}`` of every tile build, ascending, without the reserved ids -- read once from the library
+    (``ur_igemm_tile_info``), which owns the table.  ``label`` is what tells builds of one shape apart in the profile keys."""
+    global _tile_table
+    if _tile_table is None:
+        lib, info, table, tile = _lib.load(), TileInfo(), {}, 1
+        while lib.ur_igemm_tile_info(tile, C.byref(info)) == 0:  # UR_E_BADARG past the last id
+            if info.family != TILE_FAMILY_RESERVED:
+                table[tile] = (info.bm, info.bn, info.label.decode())
+            tile += 1
+        _tile_table = table
+    return _tile_table
+
 
 _zero_pages = {}
 _tune_table = None
@@ -187,8 +186,8 @@ def plan_igemm(M: int, N: int, K: int, taps: int = 1, zbatch: int = 1) -> Tuple[
     if t is None:
         per_cu = 2.5e15 / 256 * 0.4
         best, best_t = (TILE_64x64, 1), float("inf")
-        for tile in _PLANNER_TILES:
-            bm, bn, eff, _ = _TILES[tile]
+        for tile, eff in _PLANNER_TILES.items():
+            bm, bn, _ = tile_table()[tile]
             wgs = math.ceil(M / bm) * math.ceil(N / bn) * zbatch
             for sk in (1, 2, 4, 8):
                 if sk > 1 and (zbatch > 4 or K // 64 < 8 * sk):
@@ -287,7 +286,8 @@ def igemm(*, x0, w, out, M, N, K, c0, c1=0, x1=None, ldx0, ldx1=0, ldw, ldc, tap
     if e0 is not None:
         el = x0.element_size()
         z = max(zbatch, 1)
-        key = (f"igemm_{_TILES[tile][0]}x{_TILES[tile][1]}s{_TILES[tile][3]}_{'conv3x3' if taps == 9 else 'gemm'}"
+        bm, bn, label = tile_table()[tile]
+        key = (f"igemm_{bm}x{bn}s{label}_{'conv3x3' if taps == 9 else 'gemm'}"
                + ("_splitk" if splitk > 1 else "") + ("_gn" if gn is not None else ""))
         if _prof_by_shape:
             key += f"|M{M}_N{N}_K{K}_z{z}_sk{splitk}"
