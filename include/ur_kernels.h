@@ -181,7 +181,9 @@ typedef struct ur_igemm_desc {
     int32_t B, Hin, Win, Hout, Wout; /* conv geometry (taps == 9); ignored for taps == 1   */
     int32_t taps, stride, ups;
     int32_t M, N, K;
-    int32_t n_store;     /* columns written per row (>= N writes zeros), <= ldc            */
+    int32_t n_store;     /* columns written per row (>= N writes zeros), <= ldc.  The zeros come from the launch's own
+                          * column tiles, so n_store <= ceil(N / BN) * BN for the tile in use (BN: ur_igemm_tile_info), else
+                          * UR_E_BADARG before any launch: a 160-wide tile cannot pad N = 150 to 192, a 64-wide one can */
     int32_t ld_rowadd, rows_per_b;
     int32_t act;
     float out_scale;

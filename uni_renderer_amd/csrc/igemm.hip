@@ -875,6 +875,8 @@ static int igemm_run(ur_igemm_desc& d, void* stream, bool reduce = true) {
     if (d.tile == UR_TILE_AUTO) d.tile = pick_tile(d);
     if (d.tile < 1 || d.tile >= UR_TILE_COUNT) return UR_E_BADARG;
     d.ldp = padded_ldp(d, d.tile);
+    // the column grid (and the split-K slab pitch) is ceil(N / BN) tiles: zero columns up to n_store exist only inside it
+    if (d.n_store > d.ldp) return UR_E_BADARG;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     if (d.dtype == UR_DT_F16) return launch_dtype<f16>(d, s, reduce);
     if (d.dtype == UR_DT_BF16) return launch_dtype<bf16>(d, s, reduce);

@@ -218,6 +218,13 @@ def dxs_active() -> bool:
     return bool(_lib.load().ur_igemm_uses_dxs(C.byref(d)))
 
 
+def _grid_covers(tile: int, N: int, n_store: int) -> bool:
+    """The zero columns N .. n_store come from the launch's own column tiles (include/ur_kernels.h, ``n_store``): they exist
+    up to ceil(N / BN) * BN."""
+    bn = tile_table()[tile][1]
+    return -(-N // bn) * bn >= n_store
+
+
 def igemm(*, x0, w, out, M, N, K, c0, c1=0, x1=None, ldx0, ldx1=0, ldw, ldc, taps=1, conv=None, stride=1, ups=0,
           bias=None, rowadd=None, rows_per_b=0, res=None, ldres=0, n_store=0, act=ACT_NONE, out_scale=1.0,
           zbatch=1, zx=0, zw=0, zout=0, zx1=0, zbias=0, zrow=0, zres=0, zx_div=1, tile=None, splitk=None,
@@ -229,6 +236,10 @@ def igemm(*, x0, w, out, M, N, K, c0, c1=0, x1=None, ldx0, ldx1=0, ldw, ldc, tap
     lib = _lib.load()
     if tile is None or splitk is None:
         pt, ps = plan_igemm(_plan_rows if (_plan_rows is not None and taps == 1) else M, N, K, taps, zbatch)
+        if tile is None and n_store > N and not _grid_covers(pt, N, n_store):
+            # a planned tile whose grid stops short (a 160-wide one for N = 150, n_store = 192) gives way to the widest planner
+            # tile that covers; the library refuses the descriptor otherwise
+            pt = next((t for t in _PLANNER_TILES if _grid_covers(t, N, n_store)), pt)
         tile = pt if tile is None else tile
         splitk = ps if splitk is None else splitk
     d = IGemmDesc()  # zero-initialised: only what differs from 0 / NULL is written (every field set is host time,
