@@ -46,7 +46,12 @@
 extern "C" {
 #endif
 
-#define UR_ABI_VERSION 15
+/* This header is the ONE description of the ABI: the Python binding (uni_renderer_amd/_lib.py) reads it at import and derives
+ * every prototype, struct mirror and integer constant from it, and checks the loaded library against it (this version, and
+ * every ur_sizeof_X() against struct ur_X).  So it is written in the few shapes that reader accepts -- `#define UR_NAME
+ * <integer>`; structs of pointers, int32_t / int64_t / int / float and char[N] fields; functions of int / int32_t / int64_t /
+ * float and pointer parameters that return int, int64_t or const char* -- and no field is named like a Python keyword. */
+#define UR_ABI_VERSION 16
 
 #define UR_E_BADARG (-1001)   /* inconsistent descriptor (shape / alignment / null pointer)   */
 #define UR_E_UNSUPPORTED (-1002) /* shape outside what the kernels are instantiated for       */
@@ -61,7 +66,7 @@ extern "C" {
 
 /* Tile configurations of ur_igemm (rows x cols of the output tile computed by one workgroup).  These numbers are stored in
  * the tuning tables; what each id builds is ONE row of csrc/igemm_tiles.h (a new build: a #define here, a row there,
- * UR_TILE_COUNT + 1), readable at run time through ur_igemm_tile_info. */
+ * UR_TILE_COUNT + 1 -- Python sees it as ops.TILE_<name> without an edit), readable at run time through ur_igemm_tile_info. */
 #define UR_TILE_AUTO 0
 #define UR_TILE_128x128 1
 #define UR_TILE_128x64 2      /* 3-deep LDS ring */
@@ -287,14 +292,18 @@ int ur_groupnorm_apply(const void* x0, const void* x1, const void* x0_lo, const 
 
 /* The same GroupNorm in ONE launch (one workgroup per (sample, group); pivot-shifted statistics and normalisation
  * of hi + lo): for the maps of the deep levels, where stats + apply are launch-bound.  Group width (c0 + c1) / groups must be
- * even and <= 128 (UR_E_UNSUPPORTED otherwise).  Strips of at most 4 (16-byte pieces) / 8 (8- / 4-byte pieces) pieces per
- * thread are loaded once and stay in registers across the block reduction (round 6: one memory round trip); larger ones take
- * two sweeps, the second out of L2.  `silu`: bit 0 = SiLU after the affine map; bit 1 (UR_GN_TWO_SWEEP) = always the two-sweep
+ * even and <= 128 (UR_E_UNSUPPORTED otherwise).  Strips of at most 4 (16-byte pieces, bf16) / 8 (16-byte pieces, fp16) / 16
+ * (8-byte pieces) / 20 (4-byte pieces) pieces per thread, no group straddling the two sources, are loaded once and stay in
+ * registers across the block reduction (round 6: one memory round trip; ur_groupnorm_fused_resident answers which); larger
+ * ones take two sweeps, the second out of L2.  `silu`: bit 0 = SiLU after the affine map; bit 1 (UR_GN_TWO_SWEEP) = always the two-sweep
  * kernel (A/B runs, tests: the two kernels produce the same bits). */
 #define UR_GN_TWO_SWEEP 2
 int ur_groupnorm_fused(const void* x0, const void* x1, const void* x0_lo, const void* x1_lo, int c0, int c1, int B,
                        int rows, int groups, const float* gamma, const float* beta, float eps, int silu, int bper,
                        int pstride, void* out, int dtype, void* stream);
+/* Host only (ABI 16): the pieces-per-thread instantiation (2, 4, 8, 16 or 20) of the register-resident kernel that
+ * ur_groupnorm_fused launches for this shape without UR_GN_TWO_SWEEP, or 0 when it runs the two-sweep kernel (or refuses). */
+int ur_groupnorm_fused_resident(int c0, int c1, int rows, int groups, int dtype);
 
 /* LayerNorm over the last dimension of x[rows][C] (C % 8 == 0, C <= 4096), fp32 statistics.
  * rows_per_set > 0: row r uses gamma/beta + (r / rows_per_set) * pstride.  x_lo: NULL or the low part of x. */
@@ -676,7 +685,7 @@ int ur_sizeof_heads_desc(void);
  * at the end of its backward (their per-wave / per-sample partial sums are summed in one launch instead of one or two per layer). */
 #define UR_COLSUM_MULTI_MAX 96
 typedef struct ur_colsum_item {
-    const float* in;
+    const float* inp;
     float* out;
     int32_t M, N;
     int32_t pair, reserved;

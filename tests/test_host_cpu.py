@@ -485,3 +485,167 @@ def test_round5_advice_host_fixes(monkeypatch):
     assert "attr_pred" in out and "img_pred" not in out
     with pytest.raises(KeyError, match="does not run the UNet's up path"):
         out["img_pred"]
+
+
+# ---------------------------------------------------------------------------------------------
+# the binding is derived from include/ur_kernels.h (_lib.parse_header)
+# ---------------------------------------------------------------------------------------------
+def _header_text():
+    with open(os.path.join(ROOT, "include", "ur_kernels.h")) as f:
+        return f.read()
+
+
+def test_header_reader_covers_every_struct_and_constant():
+    from uni_renderer_amd import _lib, backward, ops, optim, tchain
+
+    header = _header_text()
+    structs = set(re.findall(r"typedef\s+struct\s+(\w+)", header))
+    assert len(structs) == 13 and structs == set(_lib.STRUCTS)
+    for name, cls in _lib.STRUCTS.items():
+        assert issubclass(cls, ctypes.Structure) and cls.__name__ == name and cls._fields_, name
+    defines = dict(re.findall(r"^#define\s+(UR_\w+)\s+\(?(-?\d+)\)?\s*(?:/\*.*)?$", header, flags=re.M))
+    assert len(defines) == 87 and {k: int(v) for k, v in defines.items()} == vars(_lib.ABI)
+    assert set(re.findall(r"^#define\s+(UR_\w+)", header, flags=re.M)) - {"UR_KERNELS_H"} == set(defines)  # none is left out
+    # the names the package and its tests go by are the derived classes and values
+    assert (_lib.IGemmDesc, _lib.AttnDesc, _lib.AttnBwdDesc, _lib.TChainDesc) == tuple(
+        _lib.STRUCTS[n] for n in ("ur_igemm_desc", "ur_attn_desc", "ur_attn_bwd_desc", "ur_tchain_desc"))
+    assert (ops.TileInfo, ops._AddItem, optim._Tensor) == tuple(
+        _lib.STRUCTS[n] for n in ("ur_tile_info", "ur_add_item", "ur_adamw_tensor"))
+    assert (backward._TransposeDesc, backward._CastDesc, backward._WgradDesc, backward._WgradPtrs, backward._ColsumItem,
+            backward._HeadsDesc) == tuple(_lib.STRUCTS[n] for n in (
+                "ur_transpose_desc", "ur_cast_tensor", "ur_wgrad_desc", "ur_wgrad_ptrs", "ur_colsum_item", "ur_heads_desc"))
+    assert _lib.ABI_VERSION == _lib.ABI.UR_ABI_VERSION
+    assert (ops.ACT_NONE, ops.ACT_SILU, ops.ACT_GEGLU) == (0, 1, 2) and ops.DT_ANY[torch.float32] == 2
+    assert (ops.TILE_AUTO, ops.TILE_128x128, ops.TILE_128x64, ops.TILE_64x64, ops.TILE_PP_128x320, ops.TILE_COUNT) == (0, 1, 2, 3, 49, 62)
+    assert (backward.TRANSPOSE_MAX, backward.WGRAD_GROUP_MAX, backward.COLSUM_MULTI_MAX, backward.CAST_MAX_TENSORS,
+            ops.ADD_MULTI_MAX, optim.MAX_TENSORS) == (32, 64, 96, 128, 16, 64)
+    assert (tchain.MODE_Q, tchain.MODE_FF, tchain.MODE_PRE) == (0, 1, 2)
+    # every ur_sizeof_X names a struct ur_X (what load() checks the library against)
+    sizeofs = [n for n in _lib.SYMBOLS if n.startswith("ur_sizeof_")]
+    assert len(sizeofs) == 10 and all("ur_" + n[len("ur_sizeof_"):] in _lib.STRUCTS for n in sizeofs)
+    # typed pointers: a struct parameter takes only its mirror, host-side out values their ctypes type, the rest is opaque
+    P = ctypes.POINTER
+    assert _lib.SYMBOLS["ur_wgrad_group_plan"] == (ctypes.c_int, [P(backward._WgradDesc), P(backward._WgradPtrs), ctypes.c_int,
+                                                                  P(ctypes.c_int32), P(ctypes.c_int64)])
+    assert _lib.SYMBOLS["ur_build_info"] == (ctypes.c_char_p, [])
+    assert _lib.SYMBOLS["ur_igemm_partial_floats"] == (ctypes.c_int64, [P(_lib.IGemmDesc)])
+    assert _lib.SYMBOLS["ur_add"] == (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_float, ctypes.c_void_p,
+                                                      ctypes.c_int64, ctypes.c_int, ctypes.c_void_p])
+    with pytest.raises(ctypes.ArgumentError):
+        _lib.load().ur_igemm(1234, None)  # an integer address is not a descriptor
+
+
+def test_header_reader_agrees_with_the_compiler(tmp_path):
+    """sizeof / offsetof of every field of every struct and the value of every constant, as the C++ compiler of the library
+    sees include/ur_kernels.h, against the ctypes classes and the namespace the reader derived from the same file."""
+    import subprocess
+
+    from uni_renderer_amd import _lib
+
+    lines = ["#include <cstddef>", "#include <cstdio>", '#include "ur_kernels.h"', "int main() {"]
+    for name, cls in _lib.STRUCTS.items():
+        lines.append(f'  std::printf("S {name} %zu\\n", sizeof({name}));')
+        for field, _ in cls._fields_:
+            lines.append(f'  std::printf("F {name} {field} %zu %zu\\n", offsetof({name}, {field}), sizeof((({name}*)0)->{field}));')
+    for const in vars(_lib.ABI):
+        lines.append(f'  std::printf("K {const} %lld\\n", (long long)({const}));')
+    lines += ["  return 0;", "}"]
+    src = tmp_path / "layout.cpp"
+    src.write_text("\n".join(lines) + "\n")
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")  # the Makefile's compiler, host side only
+    subprocess.run([hipcc, "-x", "c++", "-std=c++17", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(tmp_path / "layout")],
+                   check=True)
+    out = subprocess.run([str(tmp_path / "layout")], check=True, capture_output=True, text=True).stdout.split("\n")
+    seen = {"S": 0, "F": 0, "K": 0}
+    for kind, *rest in (ln.split() for ln in out if ln):
+        seen[kind] += 1
+        if kind == "S":
+            assert ctypes.sizeof(_lib.STRUCTS[rest[0]]) == int(rest[1]), rest
+        elif kind == "F":
+            f = getattr(_lib.STRUCTS[rest[0]], rest[1])
+            assert (f.offset, f.size) == (int(rest[2]), int(rest[3])), rest
+        else:
+            assert getattr(_lib.ABI, rest[0]) == int(rest[1]), rest
+    assert seen == {"S": len(_lib.STRUCTS), "F": sum(len(c._fields_) for c in _lib.STRUCTS.values()), "K": len(vars(_lib.ABI))}
+
+
+@pytest.mark.parametrize("text,what", [
+    ("int ur_f(double x);", "double x"),
+    ("int ur_f(unsigned int n);", "unsigned int n"),
+    ("typedef struct ur_s { unsigned n; } ur_s;", "ur_s"),
+    ("typedef struct ur_s { unsigned int n; } ur_s;", "ur_s"),
+    ("typedef struct ur_s { int32_t n; } ur_s;\nint ur_f(ur_s s, void* stream);", "ur_s s"),
+    ("void ur_f(int n);", "void ur_f"),
+    ("#define UR_SCALE 1.5\nint ur_f(int n);", "UR_SCALE"),
+    ("#define UR_NAME \"x\"\nint ur_f(int n);", "UR_NAME"),
+    ("#define UR_TWICE(x) (2 * (x))\nint ur_f(int n);", "UR_TWICE"),
+    ("typedef struct ur_s { const float* in; } ur_s;", "keyword"),
+    ("typedef struct ur_s { int32_t n; } ur_t;", "ur_s"),
+    ("int ur_f(int n, ...);", "..."),
+    ("int ur_f(ur_unknown* p);", "ur_unknown"),
+])
+def test_header_reader_refuses_what_it_does_not_know(text, what):
+    from uni_renderer_amd import _lib
+
+    with pytest.raises(_lib.UrLibraryError) as e:
+        _lib.parse_header(text)
+    assert what in str(e.value)
+
+
+def test_header_reader_accepts_the_shapes_the_header_uses():
+    from uni_renderer_amd import _lib
+
+    consts, structs, symbols = _lib.parse_header(
+        "#ifndef UR_KERNELS_H\n#define UR_KERNELS_H\n#define UR_A 3 /* a \\\n comment */\n#define UR_B (-7)\n"
+        'extern "C" {\ntypedef struct ur_s {\n  const void *p, *q; float* r; /* c */ int32_t a, b;\n  int64_t c; float f; char s[8]; int n;\n} ur_s;\n'
+        "int ur_f(const ur_s* d, const void* const* t, int32_t* o, const int64_t* v, float x, int64_t n,\n void* stream);\n"
+        "const char* ur_g(void); // c\nint64_t ur_h();\n}\n#endif\n")
+    assert consts == {"UR_A": 3, "UR_B": -7}
+    assert structs["ur_s"]._fields_ == [("p", ctypes.c_void_p), ("q", ctypes.c_void_p), ("r", ctypes.c_void_p), ("a", ctypes.c_int32),
+                                        ("b", ctypes.c_int32), ("c", ctypes.c_int64), ("f", ctypes.c_float), ("s", ctypes.c_char * 8),
+                                        ("n", ctypes.c_int)]
+    P = ctypes.POINTER
+    assert symbols == {"ur_f": (ctypes.c_int, [P(structs["ur_s"]), ctypes.c_void_p, P(ctypes.c_int32), P(ctypes.c_int64), ctypes.c_float,
+                                               ctypes.c_int64, ctypes.c_void_p]),
+                       "ur_g": (ctypes.c_char_p, []), "ur_h": (ctypes.c_int64, [])}
+
+
+def test_missing_header_is_as_loud_as_a_missing_library(monkeypatch):
+    from uni_renderer_amd import _lib
+
+    monkeypatch.setattr(_lib, "HEADER_PATH", os.path.join(ROOT, "include", "no_such_header.h"))
+    with pytest.raises(_lib.UrLibraryError, match="no_such_header.h"):
+        _lib._read_header()
+
+
+def test_resident_groupnorm_rule_is_the_librarys():
+    """ops.gn_resident_fits asks the library (ur_groupnorm_fused_resident, the decision launch_gn_fused takes); the rule it used to
+    repeat in Python is kept here, and the two agree over rows x group width x source split x dtype."""
+    from uni_renderer_amd import _lib, ops
+
+    def old_rule(rows, c0, c1, groups, dtype):
+        cpg = (c0 + c1) // groups
+        P = 8 if cpg % 8 == 0 else 4 if cpg % 4 == 0 else 2 if cpg % 2 == 0 else 0
+        if not P or cpg > 128 or not (c1 == 0 or c0 % cpg == 0):
+            return False
+        per_thread = (rows * (cpg // P) + 1023) // 1024
+        most = (8 if dtype == torch.float16 else 4) if P == 8 else 16 if P == 4 else 20
+        return 1 <= per_thread <= most
+
+    lib, groups, seen = _lib.load(), 32, {}
+    for rows in (1, 63, 64, 256, 1024, 4096, 16384):
+        for cpg in (1, 2, 4, 6, 8, 10, 20, 40, 128, 136):
+            Cn = cpg * groups
+            splits = [(Cn, 0), (cpg * 16, cpg * 16)]                     # one source; two, no group straddling them
+            if cpg > 1:
+                splits.append((cpg * 16 + cpg // 2, Cn - cpg * 16 - cpg // 2))  # two sources, c0 % cpg != 0
+                assert splits[-1][0] % cpg != 0
+            for c0, c1 in splits:
+                for dtype in (torch.float16, torch.bfloat16):
+                    np_ = lib.ur_groupnorm_fused_resident(c0, c1, rows, groups, ops.DT[dtype])
+                    assert np_ in (0, 2, 4, 8, 16, 20)
+                    assert bool(np_) == old_rule(rows, c0, c1, groups, dtype) == ops.gn_resident_fits(rows, c0, c1, groups, dtype), \
+                        (rows, c0, c1, dtype, np_)
+                    seen[np_] = seen.get(np_, 0) + 1
+    assert set(seen) == {0, 2, 4, 8, 16, 20}, seen  # both kernels and every instantiation are exercised
+    assert lib.ur_groupnorm_fused_resident(320, 0, 1024, 32, 2) == 0 and lib.ur_groupnorm_fused_resident(320, 0, 1024, 0, 0) == 0

@@ -22,7 +22,7 @@ import torch
 
 from . import _experiments as X
 from . import _lib, ops
-from ._lib import check
+from ._lib import ABI, check
 from .ops import DT, _ptr, _require_gpu, _stream
 
 
@@ -44,13 +44,7 @@ def transpose2d(x: torch.Tensor) -> torch.Tensor:
     return out
 
 
-class _TransposeDesc(C.Structure):
-    _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("ld_src", C.c_int64), ("bs_src", C.c_int64),
-                ("ld_dst", C.c_int64), ("bs_dst", C.c_int64), ("R", C.c_int32), ("C", C.c_int32), ("batch", C.c_int32),
-                ("rows_out", C.c_int32), ("colsum", C.c_void_p), ("colsum_ws", C.c_void_p), ("colsum_cnt", C.c_void_p)]
-
-
-_lib.register_layout("ur_sizeof_transpose_desc", _TransposeDesc)  # checked in _lib.load(), not only in a test
+_TransposeDesc = _lib.STRUCTS["ur_transpose_desc"]
 
 # Bias gradients inside the transpose launch (ur_transpose_desc.colsum): correct and deterministic, removes ~650 launches per
 # step, but every transposing workgroup then pays a memory-side store + counter round trip: 84.7 vs 84.6 ms per graphed
@@ -73,7 +67,7 @@ def _colsum_counter(device) -> torch.Tensor:
 
 
 MULTI_TRANSPOSE = X.flag("multi_transpose", True)
-TRANSPOSE_MAX = 32
+TRANSPOSE_MAX = ABI.UR_TRANSPOSE_MAX
 # W^T of the Linear weights for dx = dy . W, made in a few multi-tensor launches right after the batched cast of the weights
 # (autograd_ops.CastParams) instead of one transpose launch per layer in the backward (426 launches, 3.1 ms per step):
 # (data_ptr, shape) of the compute-dtype weight -> its transpose.  UR_EXPERIMENT=no_batch_wt: every linear_backward transposes its own.
@@ -158,8 +152,8 @@ def transpose2d_many(xs, colsum_of: Optional[int] = None, pad64=()):
     return outs if colsum_of is None else (outs, sums)
 
 
-class _CastDesc(C.Structure):
-    _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("n", C.c_int64)]
+_CastDesc = _lib.STRUCTS["ur_cast_tensor"]
+CAST_MAX_TENSORS = ABI.UR_CAST_MAX_TENSORS
 
 
 class GradSquares:
@@ -231,7 +225,7 @@ grad_sink = GradSink()
 
 
 def cast_sumsq_floats(numels) -> int:
-    """Length of the sums-of-squares output of ``cast_many(..., sumsq=True)`` over <= 128 tensors of these sizes."""
+    """Length of the sums-of-squares output of ``cast_many(..., sumsq=True)`` over <= CAST_MAX_TENSORS tensors of these sizes."""
     arr = (_CastDesc * len(numels))()
     for k, n in enumerate(numels):
         arr[k].n = int(n)
@@ -239,11 +233,11 @@ def cast_sumsq_floats(numels) -> int:
 
 
 def cast_many(srcs, dtype, sumsq: bool = False, packed: bool = False, outs=None, sumsq_out=None):
-    """``[s.to(dtype) for s in srcs]`` for fp32 -> fp16 / bf16 or fp16 / bf16 -> fp32, 128 tensors per launch
+    """``[s.to(dtype) for s in srcs]`` for fp32 -> fp16 / bf16 or fp16 / bf16 -> fp32, CAST_MAX_TENSORS tensors per launch
     (``ur_cast_multi``).  ``sumsq`` (to fp32 only): also returns the per-workgroup sums of squares of everything written,
     one 1-D fp32 tensor (``ur_cast_multi_sumsq``).  ``outs``: write into these contiguous tensors (entries may be None:
     allocated here) instead of fresh ones -- the gradient views of a bucket (GradSink).  ``sumsq_out``: write the sums of
-    squares into this fp32 tensor of ``cast_sumsq_floats`` elements (<= 128 sources: one launch) instead of a fresh one --
+    squares into this fp32 tensor of ``cast_sumsq_floats`` elements (<= CAST_MAX_TENSORS sources: one launch) instead of a fresh one --
     a fixed address that a captured clipping step can read."""
     lib = _lib.load()
     srcs = [s_.contiguous() for s_ in srcs]
@@ -272,8 +266,8 @@ def cast_many(srcs, dtype, sumsq: bool = False, packed: bool = False, outs=None,
             raise ValueError("cast_many: one source dtype per call (fp32 -> half or half -> fp32)")
     st = _stream()
     partials = []
-    for i in range(0, len(srcs), 128):
-        part = list(zip(srcs[i:i + 128], outs[i:i + 128]))
+    for i in range(0, len(srcs), CAST_MAX_TENSORS):
+        part = list(zip(srcs[i:i + CAST_MAX_TENSORS], outs[i:i + CAST_MAX_TENSORS]))
         part = [(a, b) for a, b in part if a.numel()]
         if not part:
             continue
@@ -283,7 +277,7 @@ def cast_many(srcs, dtype, sumsq: bool = False, packed: bool = False, outs=None,
         if sumsq and to_f32:
             nb = int(lib.ur_cast_multi_blocks(arr, len(part)))
             if sumsq_out is not None:
-                if len(srcs) > 128 or sumsq_out.dtype != torch.float32 or sumsq_out.numel() != nb or not sumsq_out.is_contiguous():
+                if len(srcs) > CAST_MAX_TENSORS or sumsq_out.dtype != torch.float32 or sumsq_out.numel() != nb or not sumsq_out.is_contiguous():
                     raise ValueError("cast_many(sumsq_out=...): a contiguous fp32 tensor of cast_sumsq_floats() elements")
                 ps = sumsq_out
             else:
@@ -305,7 +299,7 @@ def colsum(x: torch.Tensor, rows_per_group: int = 0) -> torch.Tensor:
     M = x.numel() // N
     groups = 1 if rows_per_group <= 0 else (M + rows_per_group - 1) // rows_per_group
     out = torch.empty(groups, N, dtype=torch.float32, device=x.device)
-    dt = 2 if x.dtype == torch.float32 else DT[x.dtype]
+    dt = ops.DT_ANY[x.dtype]
     nws = lib.ur_colsum_workspace_floats(M, N, rows_per_group)
     ws = torch.empty(nws, dtype=torch.float32, device=x.device) if nws else None
     cnt = _colsum_counter(x.device) if (COLSUM_ONE_LAUNCH and nws and lib.ur_colsum_counters(M, N, rows_per_group) <= 4096) else None
@@ -314,16 +308,7 @@ def colsum(x: torch.Tensor, rows_per_group: int = 0) -> torch.Tensor:
     return out if rows_per_group > 0 else out[0]
 
 
-class _WgradDesc(C.Structure):
-    _fields_ = [("dy", C.c_void_p), ("x", C.c_void_p), ("dw", C.c_void_p), ("db", C.c_void_p), ("partial", C.c_void_p),
-                ("zero_page", C.c_void_p), ("lddy", C.c_int64), ("ldx", C.c_int64), ("lddw", C.c_int64),
-                ("P", C.c_int32), ("N", C.c_int32), ("K", C.c_int32),
-                ("C", C.c_int32), ("B", C.c_int32), ("Hin", C.c_int32), ("Win", C.c_int32), ("Hout", C.c_int32),
-                ("Wout", C.c_int32), ("taps", C.c_int32), ("stride", C.c_int32), ("pad", C.c_int32),
-                ("splits", C.c_int32), ("tile", C.c_int32), ("zero_page_bytes", C.c_int32), ("dtype", C.c_int32)]
-
-
-_lib.register_layout("ur_sizeof_wgrad_desc", _WgradDesc)
+_WgradDesc = _lib.STRUCTS["ur_wgrad_desc"]
 
 # dW (+ db) straight from dy and x as they lie in memory (ur_wgrad: LDS transpose reads) instead of transposed copies +
 # the forward GEMM kernel.  UR_EXPERIMENT=no_wgrad restores the round-3 path (A/B: profiles/r04_wgrad_step_ab.txt).
@@ -417,11 +402,8 @@ def wgrad(dy2: torch.Tensor, x: torch.Tensor, need_bias: bool = True, conv: Opti
     return dw, db
 
 
-class _WgradPtrs(C.Structure):
-    _fields_ = [("dy", C.c_void_p), ("x", C.c_void_p), ("dw", C.c_void_p), ("db", C.c_void_p)]
-
-
-WGRAD_GROUP_MAX = 64
+_WgradPtrs = _lib.STRUCTS["ur_wgrad_ptrs"]
+WGRAD_GROUP_MAX = ABI.UR_WGRAD_GROUP_MAX
 
 
 class WgradQueue:
@@ -492,13 +474,8 @@ class WgradQueue:
                 wgrad_group(its[i:i + WGRAD_GROUP_MAX], conv=key[4], trace=self.trace)
 
 
-class _ColsumItem(C.Structure):
-    _fields_ = [("inp", C.c_void_p), ("out", C.c_void_p), ("M", C.c_int32), ("N", C.c_int32), ("pair", C.c_int32),
-                ("reserved", C.c_int32)]
-
-
-_lib.register_layout("ur_sizeof_colsum_item", _ColsumItem)
-COLSUM_MULTI_MAX = 96
+_ColsumItem = _lib.STRUCTS["ur_colsum_item"]
+COLSUM_MULTI_MAX = ABI.UR_COLSUM_MULTI_MAX
 
 
 class NormSums:
@@ -859,12 +836,7 @@ def _merge_heads(g: torch.Tensor, B: int, T: int, H: int, d: int, out: Optional[
     return out
 
 
-class _HeadsDesc(C.Structure):
-    _fields_ = [("tok", C.c_void_p), ("heads", C.c_void_p), ("ld", C.c_int64), ("off", C.c_int32), ("T", C.c_int32),
-                ("Tp", C.c_int32), ("reserved", C.c_int32)]
-
-
-_lib.register_layout("ur_sizeof_heads_desc", _HeadsDesc)
+_HeadsDesc = _lib.STRUCTS["ur_heads_desc"]
 # the per-head copies of the d = 40 flash backward (q, k, v, o, dO in; dq, dk, dv out) in one launch each way instead of 5 + 3
 HEADS_MULTI = X.flag("heads_multi", True)
 

@@ -1325,8 +1325,8 @@ __global__ void __launch_bounds__(256) colsum_multi_kernel(const ColsumMultiArgs
     float s0 = 0.f, s1 = 0.f;
     if (col < e.N) {
         int r = q;
-        for (; r + 8 < e.M; r += 16) { s0 += e.in[(int64_t)r * e.N + col]; s1 += e.in[(int64_t)(r + 8) * e.N + col]; }
-        if (r < e.M) s0 += e.in[(int64_t)r * e.N + col];
+        for (; r + 8 < e.M; r += 16) { s0 += e.inp[(int64_t)r * e.N + col]; s1 += e.inp[(int64_t)(r + 8) * e.N + col]; }
+        if (r < e.M) s0 += e.inp[(int64_t)r * e.N + col];
     }
     red[q][cl] = s0 + s1;
     __syncthreads();
@@ -1342,7 +1342,7 @@ extern "C" int ur_colsum_multi(const ur_colsum_item* items, int n, void* stream)
     ColsumMultiArgs a;
     int blocks = 0;
     for (int i = 0; i < n; ++i) {
-        if (!items[i].in || !items[i].out || items[i].M <= 0 || items[i].N <= 0 || (items[i].pair && (items[i].N & 1))) return UR_E_BADARG;
+        if (!items[i].inp || !items[i].out || items[i].M <= 0 || items[i].N <= 0 || (items[i].pair && (items[i].N & 1))) return UR_E_BADARG;
         a.t[i] = items[i];
         a.blk0[i] = blocks;
         blocks += (items[i].N + 31) / 32;

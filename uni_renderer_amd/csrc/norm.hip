@@ -763,6 +763,28 @@ extern "C" int ur_groupnorm_apply(const void* x0, const void* x1, const void* x0
     return e == hipSuccess ? 0 : -(int)e;
 }
 
+// Which kernel ur_groupnorm_fused runs: the pieces-per-thread instantiation NP of gn_resident_kernel, or 0 = gn_fused_kernel
+// (two sweeps).  Resident where the strip of a (sample, group) fits -- the bounds are the instantiations that fit 128 VGPRs
+// (1024 threads per workgroup) without spilling: 4 (bf16) / 8 (fp16) pieces of 8 channels, 16 of 4, 20 of 2 -- and no group
+// straddles the two sources.  `lo_bytes` = sizeof(lo_t<T>).  The one copy of the rule: ur_groupnorm_fused_resident exports it.
+static int gn_piece(int cpg) { return (cpg % 8 == 0) ? 8 : (cpg % 4 == 0) ? 4 : (cpg % 2 == 0) ? 2 : 0; }
+static int gn_resident_np(int c0, int c1, int rows, int groups, int lo_bytes) {
+    if (groups <= 0 || rows <= 0 || c0 + c1 < groups) return 0;
+    const int cpg = (c0 + c1) / groups;
+    const int P = gn_piece(cpg);
+    if (!P || cpg > 128) return 0;
+    const int64_t per_thread = ((int64_t)rows * (cpg / P) + GNF_THREADS - 1) / GNF_THREADS;
+    const bool whole = c1 == 0 || (c0 % cpg) == 0;
+    const int64_t most = P == 8 ? (lo_bytes == 1 ? 8 : 4) : P == 4 ? 16 : 20;
+    if (!whole || per_thread < 1 || per_thread > most) return 0;
+    return per_thread <= 2 ? 2 : per_thread <= 4 ? 4 : per_thread <= 8 ? 8 : per_thread <= 16 ? 16 : 20;
+}
+
+extern "C" int ur_groupnorm_fused_resident(int c0, int c1, int rows, int groups, int dtype) {
+    if (dtype != UR_DT_F16 && dtype != UR_DT_BF16) return 0;
+    return gn_resident_np(c0, c1, rows, groups, dtype == UR_DT_F16 ? (int)sizeof(lo_t<f16>) : (int)sizeof(lo_t<bf16>));
+}
+
 // One launch: statistics + normalisation by one workgroup per (sample, group) (csrc comment at gn_fused_kernel).
 // Meant for maps up to a few tens of MB; larger ones are faster through ur_groupnorm_stats + ur_groupnorm_apply.
 template <typename T>
@@ -773,14 +795,10 @@ static int launch_gn_fused(const void* x0, const void* x1, const void* x0_lo, co
     dim3 grid(groups, B);
     if (cpg > 128) return UR_E_UNSUPPORTED;  // the group's affine pairs are staged in a 128-entry LDS table
     {
-        // register-resident single sweep where the strip fits (<= 4 / 8 pieces per thread) and no group straddles the two sources
-        const int P = (cpg % 8 == 0) ? 8 : (cpg % 4 == 0) ? 4 : (cpg % 2 == 0) ? 2 : 0;
-        const int64_t per_thread = P ? ((int64_t)rows * (cpg / P) + GNF_THREADS - 1) / GNF_THREADS : 0;
-        const bool whole = c1 == 0 || (c0 % cpg) == 0;
-                // bounds = the instantiations that fit 128 VGPRs (1024 threads per workgroup) without spilling
-        const int64_t most = P == 8 ? (sizeof(lo_t<T>) == 1 ? 8 : 4) : P == 4 ? 16 : 20;
-        if (!(silu & 2) && P && whole && per_thread >= 1 && per_thread <= most) {
-            const int np = per_thread <= 2 ? 2 : per_thread <= 4 ? 4 : per_thread <= 8 ? 8 : per_thread <= 16 ? 16 : 20;
+        // register-resident single sweep where gn_resident_np says so
+        const int P = gn_piece(cpg);
+        const int np = (silu & UR_GN_TWO_SWEEP) ? 0 : gn_resident_np(c0, c1, rows, groups, (int)sizeof(lo_t<T>));
+        if (np) {
 #define UR_GNR(PP, NN)                                                                                                  \
     hipLaunchKernelGGL((gn_resident_kernel<T, PP, NN>), grid, dim3(GNF_THREADS), 0, s, (const T*)x0, (const T*)x1, (const lo_t<T>*)x0_lo, \
                        (const lo_t<T>*)x1_lo, c0, c1, rows, groups, gamma, beta, eps, silu & 1, bper, pstride, (T*)out, gnf_xcd())

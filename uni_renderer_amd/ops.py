@@ -14,29 +14,18 @@ import torch
 
 from . import _experiments as X
 from . import _lib
-from ._lib import AttnDesc, IGemmDesc, check
+from ._lib import ABI, AttnDesc, IGemmDesc, check
 
-DT = {torch.float16: 0, torch.bfloat16: 1}
-DT_ANY = {torch.float16: 0, torch.bfloat16: 1, torch.float32: 2}
-ACT_NONE, ACT_SILU, ACT_GEGLU = 0, 1, 2
-TILE_AUTO, TILE_128x128, TILE_128x64, TILE_64x64 = 0, 1, 2, 3
-TILE_128x128_S3, TILE_128x64_S2, TILE_64x64_S4, TILE_64x64_S2 = 4, 5, 6, 7
-TILE_PP_128x320, TILE_PP_128x320_S4, TILE_PP_256x128, TILE_PP_128x256, TILE_PP_256x256, TILE_PP_128x128, TILE_PP_256x320 = range(49, 56)
-TILE_WS320, TILE_WS320_W8 = 47, 48
+DT = {torch.float16: ABI.UR_DT_F16, torch.bfloat16: ABI.UR_DT_BF16}
+DT_ANY = {**DT, torch.float32: ABI.UR_DT_F32}
+ACT_NONE, ACT_SILU, ACT_GEGLU = ABI.UR_ACT_NONE, ABI.UR_ACT_SILU, ABI.UR_ACT_GEGLU
+# every UR_TILE_* of include/ur_kernels.h as TILE_* (TILE_AUTO, TILE_128x128, ..., TILE_FAMILY_*, TILE_COUNT)
+globals().update({name[3:]: value for name, value in vars(ABI).items() if name.startswith("UR_TILE_")})
 # which build ``conv3x3(ws=...)`` launches: 8 waves per workgroup (two instruction streams per SIMD) or 4 (one)
 WSCONV_TILE = TILE_WS320_W8 if X.number("wsconv_waves", 8) == 8 else TILE_WS320
 # the analytic planner's candidates (plan_igemm, no measured row): tile id -> relative efficiency guess
 _PLANNER_TILES = {TILE_128x128: 1.0, TILE_128x64: 0.85, TILE_64x64: 0.6}
-TILE_FAMILY_LOCKSTEP, TILE_FAMILY_WS, TILE_FAMILY_PP, TILE_FAMILY_RESERVED = 0, 1, 2, 3  # UR_TILE_FAMILY_*
-
-
-class TileInfo(C.Structure):
-    """Mirror of ``ur_tile_info``: one row of the library's table of tile builds (csrc/igemm_tiles.h)."""
-
-    _fields_ = [("bm", C.c_int32), ("bn", C.c_int32), ("family", C.c_int32), ("built", C.c_int32), ("label", C.c_char * 16)]
-
-
-_lib.register_layout("ur_sizeof_tile_info", TileInfo)
+TileInfo = _lib.STRUCTS["ur_tile_info"]  # one row of the library's table of tile builds (csrc/igemm_tiles.h)
 _tile_table = None
 
 
@@ -625,20 +614,17 @@ def resize_nearest(x, size):
 GN_FUSED_MAX_ROWS = X.number("gn_fused_max_rows", 1024)
 # round 6: small strips of the one-launch GroupNorm stay in registers (one memory round trip); no_gn_resident = always two sweeps
 GN_RESIDENT = X.flag("gn_resident", True)
-# ... and maps LARGER than GN_FUSED_MAX_ROWS pixels take the one-launch kernel too when their strips still fit in registers (the
-# 64x64 level at 320 channels: 20 four-byte pieces per thread) -- one read of the map instead of stats + apply's two
+# ... and maps of GN_FUSED_MAX_ROWS < pixels <= GN_RESIDENT_MAX_ROWS take the one-launch kernel too when their strips still fit
+# in registers (one read of the map instead of stats + apply's two).  At the default both limits are 1024, so this adds
+# nothing: the 64x64 level (4096 pixels; at 320 channels 20 four-byte pieces per thread) stays on stats + apply unless
+# UR_EXPERIMENT raises gn_resident_max_rows.
 GN_RESIDENT_MAX_ROWS = X.number("gn_resident_max_rows", 1024)
 
 
 def gn_resident_fits(rows: int, c0: int, c1: int, groups: int, dtype) -> bool:
-    """Mirror of csrc/norm.hip's launch_gn_fused: does the register-resident single-sweep kernel take this GroupNorm?"""
-    cpg = (c0 + c1) // groups
-    P = 8 if cpg % 8 == 0 else 4 if cpg % 4 == 0 else 2 if cpg % 2 == 0 else 0
-    if not P or cpg > 128 or not (c1 == 0 or c0 % cpg == 0):
-        return False
-    per_thread = (rows * (cpg // P) + 1023) // 1024
-    most = (8 if dtype == torch.float16 else 4) if P == 8 else 16 if P == 4 else 20
-    return 1 <= per_thread <= most
+    """Does ``ur_groupnorm_fused`` run this GroupNorm on the register-resident single-sweep kernel?  The library's own rule
+    (``ur_groupnorm_fused_resident``, csrc/norm.hip), host only."""
+    return bool(_lib.load().ur_groupnorm_fused_resident(c0, c1, rows, groups, DT[dtype]))
 
 
 def groupnorm(x, gamma, beta, eps, *, x1=None, groups=32, silu=False, nstat=None, napply=None, streams=1, fused=None,
@@ -663,7 +649,7 @@ def groupnorm(x, gamma, beta, eps, *, x1=None, groups=32, silu=False, nstat=None
         e0 = _prof_begin()
         check(lib.ur_groupnorm_fused(_ptr(x), _ptr(x1), _ptr(lo_of(x)), _ptr(lo_of(x1)), C0, C1, B, rows, groups,
                                      gamma.data_ptr(), beta.data_ptr(), float(eps),
-                                     int(bool(silu)) | (0 if (GN_RESIDENT if resident is None else resident) else 2),
+                                     int(bool(silu)) | (0 if (GN_RESIDENT if resident is None else resident) else ABI.UR_GN_TWO_SWEEP),
                                      (B // streams if streams > 1 else 0), (C0 + C1 if streams > 1 else 0), out.data_ptr(),
                                      DT[x.dtype], _stream()), "ur_groupnorm_fused")
         _prof_end(e0, "gn_fused", 0.0, 2.0 * out.numel() * out.element_size())
@@ -881,17 +867,12 @@ def freeu(hidden, skip, b: float, s: float, *, out=None, rows=None):
     return out
 
 
-class _AddItem(C.Structure):
-    _fields_ = [("a", C.c_void_p), ("a_lo", C.c_void_p), ("b", C.c_void_p), ("b_lo", C.c_void_p), ("out", C.c_void_p),
-                ("out_lo", C.c_void_p), ("n", C.c_int64)]
-
-
-_lib.register_layout("ur_sizeof_add_item", _AddItem)
-ADD_MULTI_MAX = 16
+_AddItem = _lib.STRUCTS["ur_add_item"]
+ADD_MULTI_MAX = ABI.UR_ADD_MULTI_MAX
 
 
 def add_multi(pairs, hilo=False):
-    """[a_i + b_i for (a_i, b_i) in pairs] in ONE launch per 16 pairs (``ur_add_hilo_multi``): the low parts of either
+    """[a_i + b_i for (a_i, b_i) in pairs] in ONE launch per ADD_MULTI_MAX pairs (``ur_add_hilo_multi``): the low parts of either
     operand are included when present, ``hilo`` also returns ``out.lo``.  All tensors of one dtype, contiguous."""
     pairs = list(pairs)
     if not pairs:

@@ -14,20 +14,16 @@ scalar): the whole training step still captures into one HIP graph.
 """
 from __future__ import annotations
 
-import ctypes as C
 from typing import Iterable, Tuple
 
 import torch
 
 from . import _lib
-from ._lib import check
+from ._lib import ABI, check
 from .ops import _stream
 
-MAX_TENSORS = 64
-
-
-class _Tensor(C.Structure):
-    _fields_ = [("p", C.c_void_p), ("g", C.c_void_p), ("m", C.c_void_p), ("v", C.c_void_p), ("n", C.c_int64)]
+MAX_TENSORS = ABI.UR_ADAMW_MAX_TENSORS
+_Tensor = _lib.STRUCTS["ur_adamw_tensor"]
 
 
 class FusedAdamW(torch.optim.Optimizer):

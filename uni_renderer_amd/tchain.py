@@ -28,9 +28,9 @@ from typing import Optional, Sequence
 import torch
 
 from . import _lib, ops
-from ._lib import TChainDesc, check
+from ._lib import ABI, TChainDesc, check
 
-MODE_Q, MODE_FF, MODE_PRE = 0, 1, 2
+MODE_Q, MODE_FF, MODE_PRE = ABI.UR_TCHAIN_Q, ABI.UR_TCHAIN_FF, ABI.UR_TCHAIN_PRE
 CH = 320           # the level the kernel is built for
 FF_HIDDEN = 4 * CH  # GEGLU hidden width the feed-forward chain is built for (TC_FF in csrc/tchain.hip)
 HEADS = 8          # heads of the head-major q / k images (ur_tchain_desc.qk_heads)
