@@ -649,3 +649,119 @@ def test_resident_groupnorm_rule_is_the_librarys():
                     seen[np_] = seen.get(np_, 0) + 1
     assert set(seen) == {0, 2, 4, 8, 16, 20}, seen  # both kernels and every instantiation are exercised
     assert lib.ur_groupnorm_fused_resident(320, 0, 1024, 32, 2) == 0 and lib.ur_groupnorm_fused_resident(320, 0, 1024, 0, 0) == 0
+
+
+# ---- the five multi-tensor launchers (csrc/ur_launch.h: one segment table, one host loop): everything below returns before a launch ----
+_P = 0x7f0000001000  # a non-null, 16-byte aligned dummy address: the host never dereferences the pointers of an item
+
+
+def _multi_launchers():
+    """name -> (function name, struct, MAX, good(item), huge(item), [spoil(item)...], tail arguments, code on grid overflow).
+    ``good`` is a small valid item; ``huge`` a valid one of 2**26 .. 2**32 workgroups, so that MAX of them pass 2**31 - 1."""
+    from uni_renderer_amd import _lib
+
+    A, S = _lib.ABI, _lib.STRUCTS
+
+    def set_(**kw):
+        return lambda d: [setattr(d, k, v) for k, v in kw.items()]
+
+    def transpose(R, C):
+        return set_(src=_P, dst=_P, ld_src=C, bs_src=R * C, ld_dst=R, bs_dst=R * C, R=R, C=C, batch=1, rows_out=0)
+
+    return {
+        "transpose": ("ur_transpose2d_multi", S["ur_transpose_desc"], A.UR_TRANSPOSE_MAX, transpose(64, 64), transpose(1 << 20, 1 << 20),
+                      [set_(src=None), set_(dst=None), set_(R=0), set_(C=-8), set_(batch=0)], (0, None), A.UR_E_BADARG),
+        "colsum": ("ur_colsum_multi", S["ur_colsum_item"], A.UR_COLSUM_MULTI_MAX, set_(inp=_P, out=_P, M=4, N=32, pair=0),
+                   set_(inp=_P, out=_P, M=4, N=2**31 - 1, pair=0), [set_(inp=None), set_(out=None), set_(M=0), set_(N=0)], (None,), A.UR_E_BADARG),
+        "adamw": ("ur_adamw_multi", S["ur_adamw_tensor"], A.UR_ADAMW_MAX_TENSORS, set_(p=_P, g=_P, m=_P, v=_P, n=100),
+                  set_(p=_P, g=_P, m=_P, v=_P, n=2**45), [set_(p=None), set_(g=None), set_(m=None), set_(v=None), set_(n=0), set_(n=-5)],
+                  (1e-3, 0.9, 0.999, 1e-8, 0.0, _P, None, None, None, None), A.UR_E_BADARG),
+        "cast": ("ur_cast_multi", S["ur_cast_tensor"], A.UR_CAST_MAX_TENSORS, set_(src=_P, dst=_P, n=100), set_(src=_P, dst=_P, n=2**45),
+                 [set_(src=None), set_(dst=None), set_(n=0), set_(n=-1)], (1, 0, None), A.UR_E_BADARG),
+        "add": ("ur_add_hilo_multi", S["ur_add_item"], A.UR_ADD_MULTI_MAX, set_(a=_P, b=_P, out=_P, n=64), set_(a=_P, b=_P, out=_P, n=2**45),
+                [set_(a=None), set_(b=None), set_(out=None), set_(n=0), set_(n=12)], (0, None), A.UR_E_UNSUPPORTED),
+    }
+
+
+@pytest.mark.parametrize("which", ["transpose", "colsum", "adamw", "cast", "add"])
+def test_multi_launchers_reject_bad_lists_and_oversized_grids_without_gpu(which):
+    from uni_renderer_amd import _lib
+
+    lib = _lib.load()
+    name, struct, nmax, good, huge, spoils, tail, overflow = _multi_launchers()[which]
+    fn, BADARG = getattr(lib, name), _lib.ABI.UR_E_BADARG
+
+    def items(n, setter):
+        arr = (struct * n)()
+        for d in arr:
+            setter(d)
+        return arr
+
+    assert fn(items(1, good), 0, *tail) == BADARG
+    assert fn(items(1, good), -1, *tail) == BADARG
+    assert fn(items(nmax + 1, good), nmax + 1, *tail) == BADARG
+    assert fn(None, 1, *tail) == BADARG
+    for n in (1, 3, nmax):  # the bad item is the LAST one: every item is validated, not only the first
+        for spoil in spoils:
+            arr = items(n, good)
+            spoil(arr[n - 1])
+            assert fn(arr, n, *tail) == BADARG, (n, spoils.index(spoil))
+    # more workgroups than one grid holds (2**31 - 1): the whole list of MAX items (for colsum and transpose only their SUM
+    # passes the limit), and an overflow behind valid small items
+    assert fn(items(nmax, huge), nmax, *tail) == overflow
+    arr = items(nmax, good)
+    for d in list(arr)[1:]:
+        huge(d)
+    assert fn(arr, nmax, *tail) == overflow
+    # an invalid item in front of the overflow is reported as such
+    arr = items(nmax, huge)
+    spoils[0](arr[0])
+    assert fn(arr, nmax, *tail) == BADARG
+
+
+def test_cast_multi_sumsq_shares_the_guards_without_gpu():
+    from uni_renderer_amd import _lib
+
+    lib = _lib.load()
+    _, struct, nmax, good, huge, _, _, _ = _multi_launchers()["cast"]
+    arr = (struct * nmax)()
+    for d in arr:
+        huge(d)
+    assert lib.ur_cast_multi_sumsq(arr, nmax, 1, 0, _P, None) == _lib.ABI.UR_E_BADARG
+    assert lib.ur_cast_multi_sumsq(arr, 1, 0, 0, _P, None) == _lib.ABI.UR_E_BADARG  # sums of squares only towards fp32
+    assert lib.ur_cast_multi_blocks(arr, 2) == 2 * 2**32
+
+
+def test_launch_chunked_slices_fills_and_checks(monkeypatch):
+    """_lib.desc_arrays / launch_chunked: 0 rows make no call, nmax rows one, nmax + 1 two (nmax and 1); ``fill`` sees the index
+    over ALL rows; the tail arguments arrive unchanged and a non-zero return raises."""
+    from types import SimpleNamespace
+
+    from uni_renderer_amd import _lib
+
+    struct, nmax = _lib.STRUCTS["ur_cast_tensor"], 4
+    calls = []
+
+    def fake(arr, n, *tail):
+        calls.append(([d.n for d in arr], n, tail))
+        return 0 if tail[0] != "fail" else _lib.ABI.UR_E_BADARG
+
+    monkeypatch.setattr(_lib, "load", lambda: SimpleNamespace(ur_fake=fake))
+    seen = []
+
+    def fill(d, row, i):
+        seen.append((row, i))
+        d.n = 100 + i
+
+    for nrows, sizes in ((0, []), (1, [1]), (nmax, [nmax]), (nmax + 1, [nmax, 1]), (2 * nmax + 3, [nmax, nmax, 3])):
+        calls.clear(), seen.clear()
+        rows = [f"row{j}" for j in range(nrows)]
+        assert _lib.launch_chunked("ur_fake", struct, rows, nmax, fill, 7, "tail") is None
+        assert [n for _, n, _ in calls] == sizes and all(len(v) == n and tail == (7, "tail") for v, n, tail in calls)
+        assert seen == [(f"row{j}", j) for j in range(nrows)]                       # every row once, with its global index
+        assert [x for v, _, _ in calls for x in v] == [100 + j for j in range(nrows)]  # ... written into its own descriptor
+        arrays = _lib.desc_arrays(struct, rows, nmax, fill)                          # the same arrays without a launch
+        assert [len(a) for a in arrays] == sizes and all(isinstance(a, struct * len(a)) for a in arrays)
+        assert len(calls) == len(sizes)
+    with pytest.raises(RuntimeError, match="ur_fake failed: UR_E_BADARG"):
+        _lib.launch_chunked("ur_fake", struct, ["r"], nmax, fill, "fail")

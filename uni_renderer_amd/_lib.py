@@ -175,3 +175,23 @@ def check(rc: int, what: str) -> None:
         else:
             msg = f"hipError {-rc}"
         raise RuntimeError(f"{what} failed: {msg}")
+
+
+def desc_arrays(struct, rows, nmax: int, fill) -> list:
+    """The descriptor arrays of a multi-tensor entry point over ``rows``: one ctypes array of ``struct`` per ``nmax`` rows,
+    after ``fill(desc, row, i)`` has set descriptor ``desc`` from ``rows[i]`` (``i`` counts over all of ``rows``)."""
+    arrays = []
+    for i in range(0, len(rows), nmax):
+        part = rows[i:i + nmax]
+        arr = (struct * len(part))()
+        for k, row in enumerate(part):
+            fill(arr[k], row, i + k)
+        arrays.append(arr)
+    return arrays
+
+
+def launch_chunked(fn_name: str, struct, rows, nmax: int, fill, *tail) -> None:
+    """``lib.fn_name(descs, n, *tail)`` once per ``nmax`` rows (``desc_arrays``), each call checked."""
+    fn = getattr(load(), fn_name)
+    for arr in desc_arrays(struct, rows, nmax, fill):
+        check(fn(arr, len(arr), *tail), fn_name)

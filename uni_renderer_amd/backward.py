@@ -117,7 +117,6 @@ def transpose2d_many(xs, colsum_of: Optional[int] = None, pad64=()):
         return transpose2d_many(xs, pad64=pad64), colsum(xs[colsum_of])
     if colsum_of is None and not pad64 and (not MULTI_TRANSPOSE or len(xs) == 1):
         return [transpose2d(x) for x in xs]
-    lib = _lib.load()
     outs, descs = [], []
     for i, x in enumerate(xs):
         _require_gpu(x)
@@ -133,22 +132,22 @@ def transpose2d_many(xs, colsum_of: Optional[int] = None, pad64=()):
         descs.append((x, out, ld, bs, Rp, Rp * Cc, R, Cc, batch))
     if len({x.dtype for x in xs}) != 1:
         raise ValueError("transpose2d_many: one dtype per call")
-    nmax = TRANSPOSE_MAX
     sums = ws = None
-    for i in range(0, len(descs), nmax):
-        part = descs[i:i + nmax]
-        arr = (_TransposeDesc * len(part))()
-        for k, (x, out, ld, bs, ldd, bsd, R, Cc, batch) in enumerate(part):
-            arr[k].src, arr[k].dst = x.data_ptr(), out.data_ptr()
-            arr[k].ld_src, arr[k].bs_src, arr[k].ld_dst, arr[k].bs_dst = ld, bs, ldd, bsd
-            arr[k].R, arr[k].C, arr[k].batch = R, Cc, batch
-            arr[k].rows_out = ldd if (i + k) in pad64 else 0
-            if colsum_of is not None and i + k == colsum_of:
-                sums = torch.empty(Cc, dtype=torch.float32, device=x.device)
-                ws = torch.empty((R + 63) // 64 * Cc, dtype=torch.float32, device=x.device)
-                arr[k].colsum, arr[k].colsum_ws = sums.data_ptr(), ws.data_ptr()
-                arr[k].colsum_cnt = _colsum_counter(x.device).data_ptr()
-        check(lib.ur_transpose2d_multi(arr, len(part), DT[xs[0].dtype], _stream()), "ur_transpose2d_multi")
+
+    def fill(d, row, i):
+        nonlocal sums, ws
+        x, out, ld, bs, ldd, bsd, R, Cc, batch = row
+        d.src, d.dst = x.data_ptr(), out.data_ptr()
+        d.ld_src, d.bs_src, d.ld_dst, d.bs_dst = ld, bs, ldd, bsd
+        d.R, d.C, d.batch = R, Cc, batch
+        d.rows_out = ldd if i in pad64 else 0
+        if colsum_of is not None and i == colsum_of:
+            sums = torch.empty(Cc, dtype=torch.float32, device=x.device)
+            ws = torch.empty((R + 63) // 64 * Cc, dtype=torch.float32, device=x.device)
+            d.colsum, d.colsum_ws = sums.data_ptr(), ws.data_ptr()
+            d.colsum_cnt = _colsum_counter(x.device).data_ptr()
+
+    _lib.launch_chunked("ur_transpose2d_multi", _TransposeDesc, descs, TRANSPOSE_MAX, fill, DT[xs[0].dtype], _stream())
     return outs if colsum_of is None else (outs, sums)
 
 
@@ -266,14 +265,15 @@ def cast_many(srcs, dtype, sumsq: bool = False, packed: bool = False, outs=None,
             raise ValueError("cast_many: one source dtype per call (fp32 -> half or half -> fp32)")
     st = _stream()
     partials = []
-    for i in range(0, len(srcs), CAST_MAX_TENSORS):
-        part = list(zip(srcs[i:i + CAST_MAX_TENSORS], outs[i:i + CAST_MAX_TENSORS]))
-        part = [(a, b) for a, b in part if a.numel()]
+
+    def fill(d, row, i):
+        d.src, d.dst, d.n = row[0].data_ptr(), row[1].data_ptr(), row[0].numel()
+
+    for i in range(0, len(srcs), CAST_MAX_TENSORS):  # (empty tensors drop out of their launch, not out of the slicing)
+        part = [(a, b) for a, b in zip(srcs[i:i + CAST_MAX_TENSORS], outs[i:i + CAST_MAX_TENSORS]) if a.numel()]
         if not part:
             continue
-        arr = (_CastDesc * len(part))()
-        for k, (a, b) in enumerate(part):
-            arr[k].src, arr[k].dst, arr[k].n = a.data_ptr(), b.data_ptr(), a.numel()
+        arr, = _lib.desc_arrays(_CastDesc, part, len(part), fill)
         if sumsq and to_f32:
             nb = int(lib.ur_cast_multi_blocks(arr, len(part)))
             if sumsq_out is not None:
@@ -514,13 +514,12 @@ class NormSums:
             self.seen = set()
         if not items:
             return
-        lib = _lib.load()
-        for i in range(0, len(items), COLSUM_MULTI_MAX):
-            chunk = items[i:i + COLSUM_MULTI_MAX]
-            arr = (_ColsumItem * len(chunk))()
-            for k, (part, out, pair) in enumerate(chunk):
-                arr[k].inp, arr[k].out, arr[k].M, arr[k].N, arr[k].pair = part.data_ptr(), out.data_ptr(), part.shape[0], part.shape[1], int(pair)
-            check(lib.ur_colsum_multi(arr, len(chunk), _stream()), "ur_colsum_multi")
+
+        def fill(d, item, i):
+            part, out, pair = item
+            d.inp, d.out, d.M, d.N, d.pair = part.data_ptr(), out.data_ptr(), part.shape[0], part.shape[1], int(pair)
+
+        _lib.launch_chunked("ur_colsum_multi", _ColsumItem, items, COLSUM_MULTI_MAX, fill, _stream())
 
 
 norm_sums = NormSums()
@@ -629,19 +628,19 @@ def rot_weights_many(ws) -> list:
     """``[_rot_weights(w, cin) for w, cin in ws]`` with 32 weights per launch (``ur_transpose2d_multi``; every weight [N, 9 cin]
     contiguous with N and cin multiples of 8): the dgrad weights of all 3x3 convs of a network right after they are packed
     (autograd_ops.PackConvWeights) instead of one launch per conv in the backward."""
-    lib = _lib.load()
     outs = [torch.empty(cin, 9 * w.shape[0], dtype=w.dtype, device=w.device) for w, cin in ws]
-    for i in range(0, len(ws), TRANSPOSE_MAX):
-        part = list(zip(ws[i:i + TRANSPOSE_MAX], outs[i:i + TRANSPOSE_MAX]))
-        arr = (_TransposeDesc * len(part))()
-        for k, ((w, cin), out) in enumerate(part):
-            N = w.shape[0]
-            if N % 8 or cin % 8 or not w.is_contiguous() or w.shape[1] != 9 * cin or w.dtype != ws[0][0].dtype:
-                raise ValueError("rot_weights_many: packed [N, 9 cin] weights of one dtype with N, cin multiples of 8")
-            arr[k].src, arr[k].dst = w.data_ptr() + 8 * cin * w.element_size(), out.data_ptr()
-            arr[k].ld_src, arr[k].bs_src, arr[k].ld_dst, arr[k].bs_dst = 9 * cin, -cin, 9 * N, N
-            arr[k].R, arr[k].C, arr[k].batch, arr[k].rows_out = N, cin, 9, 0
-        check(lib.ur_transpose2d_multi(arr, len(part), DT[ws[0][0].dtype], _stream()), "ur_transpose2d_multi")
+
+    def fill(d, row, i):
+        w, cin = row
+        N = w.shape[0]
+        if N % 8 or cin % 8 or not w.is_contiguous() or w.shape[1] != 9 * cin or w.dtype != ws[0][0].dtype:
+            raise ValueError("rot_weights_many: packed [N, 9 cin] weights of one dtype with N, cin multiples of 8")
+        d.src, d.dst = w.data_ptr() + 8 * cin * w.element_size(), outs[i].data_ptr()
+        d.ld_src, d.bs_src, d.ld_dst, d.bs_dst = 9 * cin, -cin, 9 * N, N
+        d.R, d.C, d.batch, d.rows_out = N, cin, 9, 0
+
+    if ws:
+        _lib.launch_chunked("ur_transpose2d_multi", _TransposeDesc, ws, TRANSPOSE_MAX, fill, DT[ws[0][0].dtype], _stream())
     return outs
 
 

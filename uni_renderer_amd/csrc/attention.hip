@@ -17,8 +17,7 @@
 // identical maxima, partial sums are combined once at the end).
 #include <type_traits>
 
-#include "ur_common.h"
-#include "../../include/ur_kernels.h"
+#include "ur_launch.h"
 
 namespace ur {
 
@@ -592,8 +591,7 @@ static int launch_attn32(const ur_attn_desc& d, hipStream_t s) {
         hipLaunchKernelGGL((attention32_kernel<T, D, HAS_SLOT>), grid, dim3(256), lds, s, d);
     else
         hipLaunchKernelGGL((attention32_kernel<T, D, false>), grid, dim3(256), lds, s, d);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : -(int)e;
+    return last_error();
 }
 
 template <typename T, int D>
@@ -605,8 +603,7 @@ static int launch_attn(const ur_attn_desc& d, hipStream_t s) {
     set_lds_limit_once(done, reinterpret_cast<const void*>(&attention_kernel<T, D>), (int)lds);
     dim3 grid((d.Tq + 127) / 128, d.B * d.H);
     hipLaunchKernelGGL((attention_kernel<T, D>), grid, dim3(256), lds, s, d);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : -(int)e;
+    return last_error();
 }
 
 template <typename T>
@@ -634,7 +631,5 @@ extern "C" int ur_attention(const ur_attn_desc* d, void* stream) {
     if (d->lse && !(d->scale > 0.f)) return UR_E_BADARG;  // the pre-scaled (reference slot) mode keeps no row reference
     if (d->q_hstride < 0 || d->k_hstride < 0 || (d->q_hstride & 7) || (d->k_hstride & 7)) return UR_E_BADARG;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    if (d->dtype == UR_DT_F16) return launch_attn_d<f16>(*d, s);
-    if (d->dtype == UR_DT_BF16) return launch_attn_d<bf16>(*d, s);
-    return UR_E_BADARG;
+    UR_DISPATCH(d->dtype, return launch_attn_d<T>(*d, s));
 }

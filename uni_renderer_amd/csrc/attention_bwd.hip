@@ -24,8 +24,7 @@
 // different kernels instead of one kernel with atomic dq).
 #include <cstdlib>
 
-#include "ur_common.h"
-#include "../../include/ur_kernels.h"
+#include "ur_launch.h"
 
 namespace ur {
 
@@ -815,8 +814,7 @@ static int launch_bwd32(const AttnBwdArgs& a, hipStream_t st) {
     } else {
         hipLaunchKernelGGL((attn_bwd_dkdv32_kernel<T, false, GEN>), gk, dim3(256), lds_kv, st, a);
     }
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : -(int)e;
+    return last_error();
 }
 
 template <typename T, int DP, int NBQ, int NBK, bool HAS_LSE, bool GEN>
@@ -825,8 +823,7 @@ static int launch_bwd_g(const AttnBwdArgs& a, hipStream_t st) {
     else launch_dq<T, DP, NBQ, HAS_LSE, false, GEN>(a, st);
     if (a.G > 1) launch_dkdv<T, DP, NBK, true, GEN>(a, st);
     else launch_dkdv<T, DP, NBK, false, GEN>(a, st);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : -(int)e;
+    return last_error();
 }
 template <typename T, int DP, int NBQ, int NBK, bool HAS_LSE>
 static int launch_bwd(const AttnBwdArgs& a, hipStream_t st) {

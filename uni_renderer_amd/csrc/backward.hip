@@ -7,8 +7,7 @@
 // This file holds what that needs around the GEMM -- an LDS-tiled transpose, the transposed im2col gather, column
 // sums (bias / time-embedding gradients) -- and the backward of the memory-bound ops: SiLU, GEGLU, GroupNorm(+SiLU),
 // LayerNorm.  All reductions are fixed-order (deterministic), statistics and sums in fp32.
-#include "ur_common.h"
-#include "../../include/ur_kernels.h"
+#include "ur_launch.h"
 
 namespace ur {
 
@@ -81,20 +80,15 @@ __global__ void __launch_bounds__(256) transpose2d_kernel(const T* __restrict__ 
 // apiece.  Descriptors are kernel arguments; blockIdx.x walks the concatenated tile lists.
 struct TransposeMultiArgs {
     ur_transpose_desc d[UR_TRANSPOSE_MAX];
-    int tile0[UR_TRANSPOSE_MAX + 1];
-    int n;
+    SegTable<UR_TRANSPOSE_MAX> seg;
 };
 template <typename T>
 __global__ void __launch_bounds__(256) transpose2d_multi_kernel(const TransposeMultiArgs a) {
     __shared__ __attribute__((aligned(16))) uint32_t tile[64 * 32];
-    int k = 0, hi = a.n;  // last descriptor with tile0 <= blockIdx.x
-    while (hi - k > 1) {
-        const int mid = (k + hi) >> 1;
-        if (a.tile0[mid] <= (int)blockIdx.x) k = mid; else hi = mid;
-    }
+    const int k = a.seg.find(blockIdx.x);
     const ur_transpose_desc d = a.d[k];
     const int tc = (d.C + 63) / 64, tr = (d.R + 63) / 64;
-    int id = (int)blockIdx.x - a.tile0[k];
+    int id = (int)blockIdx.x - a.seg.start[k];
     const int b = id / (tc * tr);
     id -= b * tc * tr;
     const int r0 = (id / tc) * 64, c0 = (id % tc) * 64;
@@ -990,10 +984,7 @@ __global__ void __launch_bounds__(256) resample2x_kernel(const T* __restrict__ i
     }
 }
 
-static inline int grid_for(int64_t n) {
-    int64_t g = (n + 255) / 256;
-    return (int)(g < 1 ? 1 : (g > 4096 ? 4096 : g));
-}
+constexpr int EW_BLOCKS = 4096;  // most workgroups of this file's grid-stride kernels (grid_for)
 
 }  // namespace ur
 
@@ -1065,16 +1056,6 @@ __global__ void __launch_bounds__(256) unpack_conv_weight_kernel(const T* __rest
     if (sumsq) block_partial_store(sq, sumsq);
 }
 
-#define UR_DISPATCH(dtype, CALL)                          \
-    if ((dtype) == UR_DT_F16) { typedef f16 T; CALL; }    \
-    else if ((dtype) == UR_DT_BF16) { typedef bf16 T; CALL; } \
-    else return UR_E_BADARG;
-
-static int last_error() {
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : -(int)e;
-}
-
 extern "C" int ur_transpose2d(const void* src, int64_t ld_src, int64_t bs_src, void* dst, int64_t ld_dst, int64_t bs_dst,
                               int R, int C, int batch, int dtype, void* stream) {
     if (!src || !dst || R <= 0 || C <= 0 || batch <= 0 || (C & 7) || (ld_src & 7) || (ld_dst & 7) || (bs_src & 7) ||
@@ -1090,25 +1071,18 @@ extern "C" int ur_transpose2d(const void* src, int64_t ld_src, int64_t bs_src, v
 extern "C" int ur_sizeof_transpose_desc(void) { return (int)sizeof(ur_transpose_desc); }
 
 extern "C" int ur_transpose2d_multi(const ur_transpose_desc* descs, int n, int dtype, void* stream) {
-    if (!descs || n <= 0 || n > UR_TRANSPOSE_MAX) return UR_E_BADARG;
     TransposeMultiArgs a;
-    int64_t tiles = 0;
-    for (int i = 0; i < n; ++i) {
-        const ur_transpose_desc& d = descs[i];
+    const int rc = pack(descs, n, a.d, a.seg, UR_E_BADARG, [](const ur_transpose_desc& d) -> int64_t {
         if (!d.src || !d.dst || d.R <= 0 || d.C <= 0 || d.batch <= 0 || (d.C & 7) || (d.ld_src & 7) || (d.ld_dst & 7) ||
             (d.bs_src & 7) || (d.bs_dst & 7) || d.ld_dst < ((d.R + 7) & ~7))
-            return UR_E_BADARG;
-        if (d.colsum && (d.batch != 1 || !d.colsum_ws || !d.colsum_cnt)) return UR_E_BADARG;
-        if (d.rows_out && ((d.rows_out & 7) || d.rows_out < d.R || d.rows_out > ((d.R + 63) & ~63) || d.ld_dst < d.rows_out)) return UR_E_BADARG;
-        a.d[i] = d;
-        a.tile0[i] = (int)tiles;
-        tiles += (int64_t)((d.C + 63) / 64) * ((d.R + 63) / 64) * d.batch;
-        if (tiles > 0x7fffffff) return UR_E_BADARG;
-    }
-    a.tile0[n] = (int)tiles;
-    a.n = n;
+            return 0;
+        if (d.colsum && (d.batch != 1 || !d.colsum_ws || !d.colsum_cnt)) return 0;
+        if (d.rows_out && ((d.rows_out & 7) || d.rows_out < d.R || d.rows_out > ((d.R + 63) & ~63) || d.ld_dst < d.rows_out)) return 0;
+        return (int64_t)((d.C + 63) / 64) * ((d.R + 63) / 64) * d.batch;
+    });
+    if (rc) return rc;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    UR_DISPATCH(dtype, hipLaunchKernelGGL((transpose2d_multi_kernel<T>), dim3((unsigned)tiles), dim3(256), 0, s, a));
+    UR_DISPATCH(dtype, hipLaunchKernelGGL((transpose2d_multi_kernel<T>), dim3(a.seg.total()), dim3(256), 0, s, a));
     return last_error();
 }
 
@@ -1197,7 +1171,7 @@ extern "C" int ur_colsum(const void* x, int64_t ldx, int M, int N, int rows_per_
 extern "C" int ur_silu_backward(const void* x, const void* dy, void* dx, int64_t n, int dtype, void* stream) {
     if (!x || !dy || !dx || n <= 0 || (n & 7)) return UR_E_BADARG;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    UR_DISPATCH(dtype, hipLaunchKernelGGL((silu_bwd_kernel<T>), dim3(grid_for(n / 8)), dim3(256), 0, s, (const T*)x,
+    UR_DISPATCH(dtype, hipLaunchKernelGGL((silu_bwd_kernel<T>), dim3(grid_for(n / 8, EW_BLOCKS)), dim3(256), 0, s, (const T*)x,
                                           (const T*)dy, (T*)dx, n / 8));
     return last_error();
 }
@@ -1205,7 +1179,7 @@ extern "C" int ur_silu_backward(const void* x, const void* dy, void* dx, int64_t
 extern "C" int ur_geglu_forward(const void* h, void* y, int64_t M, int D, int dtype, void* stream) {
     if (!h || !y || M <= 0 || D <= 0 || (D & 7)) return UR_E_BADARG;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    UR_DISPATCH(dtype, hipLaunchKernelGGL((geglu_fwd_kernel<T>), dim3(grid_for(M * (D / 8))), dim3(256), 0, s, (const T*)h,
+    UR_DISPATCH(dtype, hipLaunchKernelGGL((geglu_fwd_kernel<T>), dim3(grid_for(M * (D / 8), EW_BLOCKS)), dim3(256), 0, s, (const T*)h,
                                           (T*)y, M, D));
     return last_error();
 }
@@ -1213,7 +1187,7 @@ extern "C" int ur_geglu_forward(const void* h, void* y, int64_t M, int D, int dt
 extern "C" int ur_geglu_backward(const void* h, const void* dy, void* dh, int64_t M, int D, int dtype, void* stream) {
     if (!h || !dy || !dh || M <= 0 || D <= 0 || (D & 7)) return UR_E_BADARG;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    UR_DISPATCH(dtype, hipLaunchKernelGGL((geglu_bwd_kernel<T>), dim3(grid_for(M * (D / 8))), dim3(256), 0, s, (const T*)h,
+    UR_DISPATCH(dtype, hipLaunchKernelGGL((geglu_bwd_kernel<T>), dim3(grid_for(M * (D / 8), EW_BLOCKS)), dim3(256), 0, s, (const T*)h,
                                           (const T*)dy, (T*)dh, M, D));
     return last_error();
 }
@@ -1287,7 +1261,7 @@ extern "C" int ur_split_heads(const void* x, int64_t ld, int off, int B, int T_,
         return UR_E_BADARG;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const int64_t total = (int64_t)B * H * Tp * (dp / 8);
-    UR_DISPATCH(dtype, hipLaunchKernelGGL((split_heads_kernel<T>), dim3(grid_for(total)), dim3(256), 0, s, (const T*)x, ld, off,
+    UR_DISPATCH(dtype, hipLaunchKernelGGL((split_heads_kernel<T>), dim3(grid_for(total, EW_BLOCKS)), dim3(256), 0, s, (const T*)x, ld, off,
                                           B, T_, H, d, (T*)out, Tp, dp));
     return last_error();
 }
@@ -1298,7 +1272,7 @@ extern "C" int ur_merge_heads(const void* g, int Tp, int dp, int B, int T_, int 
         return UR_E_BADARG;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const int64_t total = (int64_t)B * H * T_ * (d / 8);
-    UR_DISPATCH(dtype, hipLaunchKernelGGL((merge_heads_kernel<T>), dim3(grid_for(total)), dim3(256), 0, s, (const T*)g, Tp, dp, B,
+    UR_DISPATCH(dtype, hipLaunchKernelGGL((merge_heads_kernel<T>), dim3(grid_for(total, EW_BLOCKS)), dim3(256), 0, s, (const T*)g, Tp, dp, B,
                                           T_, H, d, (T*)out, ld, off));
     return last_error();
 }
@@ -1309,19 +1283,14 @@ extern "C" int ur_merge_heads(const void* g, int Tp, int dp, int B, int T_, int 
 // result is planar, out[k * C + c] (ur_pairsum_rows).
 struct ColsumMultiArgs {
     ur_colsum_item t[UR_COLSUM_MULTI_MAX];
-    int blk0[UR_COLSUM_MULTI_MAX + 1];
-    int n;
+    SegTable<UR_COLSUM_MULTI_MAX> seg;
 };
 __global__ void __launch_bounds__(256) colsum_multi_kernel(const ColsumMultiArgs a) {
     __shared__ float red[8][32];
-    int lo = 0, hi = a.n;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (a.blk0[mid] <= (int)blockIdx.x) lo = mid; else hi = mid;
-    }
-    const ur_colsum_item e = a.t[lo];
+    const int k = a.seg.find(blockIdx.x);
+    const ur_colsum_item e = a.t[k];
     const int cl = threadIdx.x & 31, q = threadIdx.x >> 5;   // 32 columns x 8 row lanes: 128-byte row segments
-    const int col = ((int)blockIdx.x - a.blk0[lo]) * 32 + cl;
+    const int col = ((int)blockIdx.x - a.seg.start[k]) * 32 + cl;
     float s0 = 0.f, s1 = 0.f;
     if (col < e.N) {
         int r = q;
@@ -1338,18 +1307,13 @@ __global__ void __launch_bounds__(256) colsum_multi_kernel(const ColsumMultiArgs
     }
 }
 extern "C" int ur_colsum_multi(const ur_colsum_item* items, int n, void* stream) {
-    if (!items || n <= 0 || n > UR_COLSUM_MULTI_MAX) return UR_E_BADARG;
     ColsumMultiArgs a;
-    int blocks = 0;
-    for (int i = 0; i < n; ++i) {
-        if (!items[i].inp || !items[i].out || items[i].M <= 0 || items[i].N <= 0 || (items[i].pair && (items[i].N & 1))) return UR_E_BADARG;
-        a.t[i] = items[i];
-        a.blk0[i] = blocks;
-        blocks += (items[i].N + 31) / 32;
-    }
-    a.blk0[n] = blocks;
-    a.n = n;
-    hipLaunchKernelGGL(colsum_multi_kernel, dim3(blocks), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), a);
+    const int rc = pack(items, n, a.t, a.seg, UR_E_BADARG, [](const ur_colsum_item& e) -> int64_t {
+        if (!e.inp || !e.out || e.M <= 0 || e.N <= 0 || (e.pair && (e.N & 1))) return 0;
+        return ((int64_t)e.N + 31) / 32;
+    });
+    if (rc) return rc;
+    hipLaunchKernelGGL(colsum_multi_kernel, dim3(a.seg.total()), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), a);
     return last_error();
 }
 extern "C" int ur_sizeof_colsum_item(void) { return (int)sizeof(ur_colsum_item); }
@@ -1367,7 +1331,7 @@ static int heads_multi(const ur_heads_desc* descs, int n, int B, int H, int d, i
     }
     a.n = n; a.B = B; a.H = H; a.d = d; a.dp = dp;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    const dim3 grid(grid_for(most), n);
+    const dim3 grid(grid_for(most, EW_BLOCKS), n);
     if (split) { UR_DISPATCH(dtype, hipLaunchKernelGGL((split_heads_multi_kernel<T>), grid, dim3(256), 0, s, a)); }
     else { UR_DISPATCH(dtype, hipLaunchKernelGGL((merge_heads_multi_kernel<T>), grid, dim3(256), 0, s, a)); }
     return last_error();
@@ -1400,7 +1364,7 @@ extern "C" int ur_softmax_backward_rows(const void* p, void* dp, int64_t ld, int
 extern "C" int ur_silu_forward(const void* x, void* y, int64_t n, int dtype, void* stream) {
     if (!x || !y || n <= 0 || (n & 7)) return UR_E_BADARG;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    UR_DISPATCH(dtype, hipLaunchKernelGGL((silu_fwd_kernel<T>), dim3(grid_for(n / 8)), dim3(256), 0, s, (const T*)x, (T*)y, n / 8));
+    UR_DISPATCH(dtype, hipLaunchKernelGGL((silu_fwd_kernel<T>), dim3(grid_for(n / 8, EW_BLOCKS)), dim3(256), 0, s, (const T*)x, (T*)y, n / 8));
     return last_error();
 }
 
@@ -1409,7 +1373,7 @@ extern "C" int ur_resample2x(const void* in, void* out, int B, int Hout, int Wou
     if (mode != 1 && ((Hout | Wout) & 1)) return UR_E_BADARG;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const int64_t total = (int64_t)B * Hout * Wout * (C / 8);
-    UR_DISPATCH(dtype, hipLaunchKernelGGL((resample2x_kernel<T>), dim3(grid_for(total)), dim3(256), 0, s, (const T*)in, (T*)out, B,
+    UR_DISPATCH(dtype, hipLaunchKernelGGL((resample2x_kernel<T>), dim3(grid_for(total, EW_BLOCKS)), dim3(256), 0, s, (const T*)in, (T*)out, B,
                                           Hout, Wout, C, mode));
     return last_error();
 }
@@ -1450,8 +1414,7 @@ extern "C" int ur_unpack_conv_weight_grad(const void* dwp, int64_t ld, float* ou
 // ---------------------------------------------------------------------------------------------------------------
 struct AdamwArgs {
     ur_adamw_tensor t[UR_ADAMW_MAX_TENSORS];
-    int chunk0[UR_ADAMW_MAX_TENSORS + 1];
-    int n;
+    SegTable<UR_ADAMW_MAX_TENSORS> seg;
     float lr, beta1, beta2, eps, wd;
     const float *step, *grad_scale, *found_inf;
     const float* hyper;  // NULL, or device {lr, weight_decay}: read at run time instead of the by-value arguments
@@ -1469,13 +1432,9 @@ __device__ __forceinline__ void adamw_one(float& p, float g, float& m, float& v,
 
 __global__ void __launch_bounds__(256) adamw_multi_kernel(const AdamwArgs a) {
     if (a.found_inf && *a.found_inf != 0.f) return;
-    int lo = 0, hi = a.n;  // last tensor with chunk0 <= blockIdx.x
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (a.chunk0[mid] <= (int)blockIdx.x) lo = mid; else hi = mid;
-    }
-    const ur_adamw_tensor t = a.t[lo];
-    const int64_t beg = (int64_t)((int)blockIdx.x - a.chunk0[lo]) * ADAMW_CHUNK;
+    const int k = a.seg.find(blockIdx.x);
+    const ur_adamw_tensor t = a.t[k];
+    const int64_t beg = (int64_t)((int)blockIdx.x - a.seg.start[k]) * ADAMW_CHUNK;
     const int64_t end = beg + ADAMW_CHUNK < t.n ? beg + ADAMW_CHUNK : t.n;
     const float step = *a.step;
     // 1 - beta^step in double: beta2 = 0.999 at step 1 leaves 1e-3, which fp32 v_log / v_exp resolve to 1e-4 relative only
@@ -1516,23 +1475,17 @@ __global__ void __launch_bounds__(256) adamw_multi_kernel(const AdamwArgs a) {
 extern "C" int ur_adamw_multi(const ur_adamw_tensor* tensors, int n_tensors, float lr, float beta1, float beta2, float eps,
                               float weight_decay, const float* step, const float* grad_scale, const float* found_inf,
                               const float* hyper, void* stream) {
-    if (!tensors || n_tensors <= 0 || n_tensors > UR_ADAMW_MAX_TENSORS || !step || !(beta1 >= 0.f && beta1 < 1.f) ||
-        !(beta2 >= 0.f && beta2 < 1.f))  // the same range torch.optim.AdamW (and optim.FusedAdamW) accept
+    if (!step || !(beta1 >= 0.f && beta1 < 1.f) || !(beta2 >= 0.f && beta2 < 1.f))  // the range torch.optim.AdamW (and optim.FusedAdamW) accept
         return UR_E_BADARG;
     AdamwArgs a;
-    int64_t chunks = 0;
-    for (int i = 0; i < n_tensors; ++i) {
-        if (!tensors[i].p || !tensors[i].g || !tensors[i].m || !tensors[i].v || tensors[i].n <= 0) return UR_E_BADARG;
-        a.t[i] = tensors[i];
-        a.chunk0[i] = (int)chunks;
-        chunks += (tensors[i].n + ADAMW_CHUNK - 1) / ADAMW_CHUNK;
-        if (chunks > 0x7fffffff) return UR_E_BADARG;
-    }
-    a.chunk0[n_tensors] = (int)chunks;
-    a.n = n_tensors;
+    const int rc = pack(tensors, n_tensors, a.t, a.seg, UR_E_BADARG, [](const ur_adamw_tensor& t) -> int64_t {
+        if (!t.p || !t.g || !t.m || !t.v || t.n <= 0) return 0;
+        return (t.n + ADAMW_CHUNK - 1) / ADAMW_CHUNK;
+    });
+    if (rc) return rc;
     a.lr = lr; a.beta1 = beta1; a.beta2 = beta2; a.eps = eps; a.wd = weight_decay;
     a.step = step; a.grad_scale = grad_scale; a.found_inf = found_inf; a.hyper = hyper;
-    hipLaunchKernelGGL(adamw_multi_kernel, dim3((unsigned)chunks), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), a);
+    hipLaunchKernelGGL(adamw_multi_kernel, dim3(a.seg.total()), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), a);
     return last_error();
 }
 
@@ -1541,21 +1494,16 @@ extern "C" int ur_adamw_multi(const ur_adamw_tensor* tensors, int n_tensors, flo
 // ---------------------------------------------------------------------------------------------------------------
 struct CastArgs {
     ur_cast_tensor t[UR_CAST_MAX_TENSORS];
-    int chunk0[UR_CAST_MAX_TENSORS + 1];
-    int n;
+    SegTable<UR_CAST_MAX_TENSORS> seg;
     float* sumsq;  // to_f32 only: per-workgroup sum of squares of the values written (NULL: none)
 };
 constexpr int CAST_CHUNK = 8192;
 
 template <typename T, bool TO_F32>
 __global__ void __launch_bounds__(256) cast_multi_kernel(const CastArgs a) {
-    int lo = 0, hi = a.n;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (a.chunk0[mid] <= (int)blockIdx.x) lo = mid; else hi = mid;
-    }
-    const ur_cast_tensor t = a.t[lo];
-    const int64_t beg = (int64_t)((int)blockIdx.x - a.chunk0[lo]) * CAST_CHUNK;
+    const int k = a.seg.find(blockIdx.x);
+    const ur_cast_tensor t = a.t[k];
+    const int64_t beg = (int64_t)((int)blockIdx.x - a.seg.start[k]) * CAST_CHUNK;
     const int64_t end = beg + CAST_CHUNK < t.n ? beg + CAST_CHUNK : t.n;
     const bool vec = ((((uintptr_t)t.src) | ((uintptr_t)t.dst)) & 15) == 0;
     const int64_t end8 = vec ? beg + ((end - beg) & ~(int64_t)7) : beg;
@@ -1601,24 +1549,20 @@ extern "C" int64_t ur_cast_multi_blocks(const ur_cast_tensor* tensors, int n_ten
 }
 
 extern "C" int ur_cast_multi_sumsq(const ur_cast_tensor* tensors, int n_tensors, int to_f32, int dtype, float* sumsq, void* stream) {
-    if (!tensors || n_tensors <= 0 || n_tensors > UR_CAST_MAX_TENSORS || (sumsq && !to_f32)) return UR_E_BADARG;
+    if (sumsq && !to_f32) return UR_E_BADARG;
     CastArgs a;
     a.sumsq = sumsq;
-    int64_t chunks = 0;
-    for (int i = 0; i < n_tensors; ++i) {
-        if (!tensors[i].src || !tensors[i].dst || tensors[i].n <= 0) return UR_E_BADARG;
-        a.t[i] = tensors[i];
-        a.chunk0[i] = (int)chunks;
-        chunks += (tensors[i].n + CAST_CHUNK - 1) / CAST_CHUNK;
-        if (chunks > 0x7fffffff) return UR_E_BADARG;
-    }
-    a.chunk0[n_tensors] = (int)chunks;
-    a.n = n_tensors;
+    const int rc = pack(tensors, n_tensors, a.t, a.seg, UR_E_BADARG, [](const ur_cast_tensor& t) -> int64_t {
+        if (!t.src || !t.dst || t.n <= 0) return 0;
+        return (t.n + CAST_CHUNK - 1) / CAST_CHUNK;
+    });
+    if (rc) return rc;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const dim3 grid(a.seg.total());
     if (to_f32) {
-        UR_DISPATCH(dtype, hipLaunchKernelGGL((cast_multi_kernel<T, true>), dim3((unsigned)chunks), dim3(256), 0, s, a));
+        UR_DISPATCH(dtype, hipLaunchKernelGGL((cast_multi_kernel<T, true>), grid, dim3(256), 0, s, a));
     } else {
-        UR_DISPATCH(dtype, hipLaunchKernelGGL((cast_multi_kernel<T, false>), dim3((unsigned)chunks), dim3(256), 0, s, a));
+        UR_DISPATCH(dtype, hipLaunchKernelGGL((cast_multi_kernel<T, false>), grid, dim3(256), 0, s, a));
     }
     return last_error();
 }

@@ -19,8 +19,7 @@
 // (maps of up to 256 pixels are one chain), then four pairwise levels over the 16 pixel lanes of a wave and a pairwise add of
 // the 4 waves: at most min(4, ceil(HW / 64)) + 2 + ceil(log2 min(HW, 256)) roundings per sum for any map size.
 // The row and column twiddles (H + W pairs) are computed once per workgroup into LDS when H + W <= 1024.
-#include "ur_common.h"
-#include "../../include/ur_kernels.h"
+#include "ur_launch.h"
 
 namespace ur {
 
@@ -328,8 +327,7 @@ static int freeu_launch(const FreeuArgs& a, int blocks, hipStream_t s) {
     else if (HW <= 256) hipLaunchKernelGGL((freeu_kernel<T, 4>), dim3(blocks), dim3(256), 0, s, a);
     else if (HW <= 1024) hipLaunchKernelGGL((freeu_kernel<T, 16>), dim3(blocks), dim3(256), 0, s, a);
     else hipLaunchKernelGGL((freeu_kernel<T, 0>), dim3(blocks), dim3(256), 0, s, a);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : -(int)e;
+    return last_error();
 }
 
 }  // namespace ur
@@ -362,5 +360,5 @@ extern "C" int ur_freeu(void* hidden, void* hidden_lo, int Ch, float b, const vo
         if (blocks > (1 << 30)) return UR_E_UNSUPPORTED;
     }
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    return dtype == UR_DT_F16 ? freeu_launch<f16>(a, (int)blocks, st) : freeu_launch<bf16>(a, (int)blocks, st);
+    UR_DISPATCH(dtype, return freeu_launch<T>(a, (int)blocks, st));
 }

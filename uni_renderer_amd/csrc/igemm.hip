@@ -22,6 +22,7 @@
 
 #include "igemm_epi.h"
 #include "igemm_tiles.h"
+#include "ur_launch.h"
 
 namespace ur {
 
@@ -692,8 +693,7 @@ static int launch_splitk_reduce(const ur_igemm_desc& d, hipStream_t s) {
     if (blocks > 4096) blocks = 4096;
     if (total * d.zbatch < REDUCE_PIPE_MAX_THREADS) hipLaunchKernelGGL((igemm_splitk_reduce<T, true>), dim3(blocks, d.zbatch), dim3(256), 0, s, d);
     else hipLaunchKernelGGL((igemm_splitk_reduce<T, false>), dim3(blocks, d.zbatch), dim3(256), 0, s, d);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : -(int)e;
+    return last_error();
 }
 
 template <typename T, int BM, int BN, int WM, int WN, int NSTAGE, int MF, int NL>
@@ -701,7 +701,6 @@ static int launch_cfg(const ur_igemm_desc& d, hipStream_t s, bool reduce) {
     const int tiles_m = (d.M + BM - 1) / BM, tiles_n = (d.N + BN - 1) / BN;
     dim3 grid(tiles_m * tiles_n, 1, d.zbatch * d.splitk);
     const size_t lds = (NSTAGE > 0 ? NSTAGE : 2) * (BM + BN) * 128;
-    hipError_t e;
     if (d.taps == 9) {
         ensure_lds_limit<T, BM, BN, WM, WN, NSTAGE, true, MF, NL>((int)lds);
         hipLaunchKernelGGL((igemm_kernel<T, BM, BN, WM, WN, NSTAGE, true, MF, NL>), grid, dim3((WM * WN + NL) * 64), lds, s, d);
@@ -709,8 +708,8 @@ static int launch_cfg(const ur_igemm_desc& d, hipStream_t s, bool reduce) {
         ensure_lds_limit<T, BM, BN, WM, WN, NSTAGE, false, MF, NL>((int)lds);
         hipLaunchKernelGGL((igemm_kernel<T, BM, BN, WM, WN, NSTAGE, false, MF, NL>), grid, dim3((WM * WN + NL) * 64), lds, s, d);
     }
-    e = hipGetLastError();
-    if (e != hipSuccess) return -(int)e;
+    const int rc = last_error();
+    if (rc) return rc;
     if (d.splitk > 1 && reduce) return launch_splitk_reduce<T>(d, s);
     return 0;
 }
@@ -878,9 +877,7 @@ static int igemm_run(ur_igemm_desc& d, void* stream, bool reduce = true) {
     // the column grid (and the split-K slab pitch) is ceil(N / BN) tiles: zero columns up to n_store exist only inside it
     if (d.n_store > d.ldp) return UR_E_BADARG;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    if (d.dtype == UR_DT_F16) return launch_dtype<f16>(d, s, reduce);
-    if (d.dtype == UR_DT_BF16) return launch_dtype<bf16>(d, s, reduce);
-    return UR_E_BADARG;
+    UR_DISPATCH(d.dtype, return launch_dtype<T>(d, s, reduce));
 }
 
 // 1 when ur_igemm would run this conv on the dx-tap-sharing kernel (igemm_dxs.hip), 0 otherwise -- for tests and tools
@@ -913,10 +910,7 @@ extern "C" int ur_igemm_splitk_gn(const ur_igemm_desc* din, const float* gamma, 
     if (d.splitk <= 1) return UR_E_BADARG;  // (clamped away: K too short for a split)
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const dim3 grid(groups, d.B, d.zbatch);
-    if (d.dtype == UR_DT_F16)
-        hipLaunchKernelGGL((igemm_splitk_reduce_gn<f16>), grid, dim3(RGN_THREADS), 0, s, d, gamma, beta, zgn, eps, groups, silu, rows);
-    else
-        hipLaunchKernelGGL((igemm_splitk_reduce_gn<bf16>), grid, dim3(RGN_THREADS), 0, s, d, gamma, beta, zgn, eps, groups, silu, rows);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : -(int)e;
+    UR_DISPATCH(d.dtype, hipLaunchKernelGGL((igemm_splitk_reduce_gn<T>), grid, dim3(RGN_THREADS), 0, s, d, gamma, beta, zgn, eps,
+                                            groups, silu, rows));
+    return last_error();
 }

@@ -21,6 +21,7 @@
 // the UNets at 64x64 .. 8x8, including the nearest-2x fused upsample convs); everything else stays on igemm.hip.
 #include "igemm_epi.h"
 #include "igemm_tiles.h"
+#include "ur_launch.h"
 
 // -DUR_DXS_ABLATE=<bits>: timing-only builds (results are garbage; tools/experiments/r04_run13.sh):
 //   1 = the pixel block is never copied, 2 = fragment reads at the unshifted rows (address math hoisted out of the loop),
@@ -350,8 +351,7 @@ static int dxs_launch_cfg(const ur_igemm_desc& d, hipStream_t s) {
     static std::atomic<uint64_t> done{0};
     set_lds_limit_once(done, reinterpret_cast<const void*>(&igemm_dxs_kernel<T, BM, BN, WM, WN>), lds);
     hipLaunchKernelGGL((igemm_dxs_kernel<T, BM, BN, WM, WN>), grid, dim3(WM * WN * 64), lds, s, d);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : -(int)e;
+    return last_error();
 }
 
 template <typename T>
@@ -378,9 +378,7 @@ int igemm_dxs_tile_bm(int tile) {
 
 // main pass (the caller, igemm.hip, runs the shared split-K second pass)
 int igemm_dxs_launch(const ur_igemm_desc& d, hipStream_t s) {
-    if (d.dtype == UR_DT_F16) return dxs_launch_dtype<f16>(d, s);
-    if (d.dtype == UR_DT_BF16) return dxs_launch_dtype<bf16>(d, s);
-    return UR_E_BADARG;
+    UR_DISPATCH(d.dtype, return dxs_launch_dtype<T>(d, s));
 }
 
 }  // namespace ur

@@ -28,6 +28,7 @@
 // weight tile as operand A; weight rows permuted inside 32-blocks so that a lane ends with 16 consecutive channels of one
 // pixel -- igemm.hip's MF = 32 layout, epilogue shared (igemm_epi.h).
 #include "igemm_epi.h"
+#include "ur_launch.h"
 
 namespace ur {
 
@@ -433,8 +434,7 @@ static int pp_launch_cfg(const ur_igemm_desc& d, hipStream_t s) {
         set_lds_limit_once(done, reinterpret_cast<const void*>(&igemm_pp_kernel<T, BM, BN, WM, WN, NS, false>), lds);
         hipLaunchKernelGGL((igemm_pp_kernel<T, BM, BN, WM, WN, NS, false>), grid, dim3(512), lds, s, d);
     }
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : -(int)e;
+    return last_error();
 }
 
 template <typename T>
@@ -453,9 +453,7 @@ static int pp_launch_dtype(const ur_igemm_desc& d, hipStream_t s) {
 
 // main pass of a ping-pong tile (the caller, igemm.hip, runs the shared split-K second pass)
 int igemm_pp_launch(const ur_igemm_desc& d, hipStream_t s) {
-    if (d.dtype == UR_DT_F16) return pp_launch_dtype<f16>(d, s);
-    if (d.dtype == UR_DT_BF16) return pp_launch_dtype<bf16>(d, s);
-    return UR_E_BADARG;
+    UR_DISPATCH(d.dtype, return pp_launch_dtype<T>(d, s));
 }
 
 }  // namespace ur

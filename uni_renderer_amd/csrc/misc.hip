@@ -1,7 +1,6 @@
 // Small HBM-bound helpers: elementwise add (the enc->unet skip exchange), sinusoidal timestep
 // embedding, and NCHW <-> NHWC layout glue at the module boundary.
-#include "ur_common.h"
-#include "../../include/ur_kernels.h"
+#include "ur_launch.h"
 
 namespace ur {
 
@@ -68,11 +67,7 @@ __global__ void __launch_bounds__(256) nhwc_to_nchw_kernel(const T* __restrict__
     }
 }
 
-static inline int grid_for(int64_t n) {
-    int64_t g = (n + 255) / 256;
-    return (int)(g < 1 ? 1 : (g > 2048 ? 2048 : g));
-}
-
+constexpr int EW_BLOCKS = 2048;  // most workgroups of this file's grid-stride kernels (grid_for)
 
 // out[b][oy][ox][:] = in[b][sy(oy)][sx(ox)][:] with PyTorch's 'nearest' rule: s(o) = min(floor(o * (float)in / out), in - 1)
 // (F.interpolate(size=...) of Upsample2D when the latent side is not a multiple of 8, controlnet.py:1129-1130).
@@ -103,16 +98,9 @@ extern "C" int ur_add(const void* a, const void* b, float alpha, void* out, int6
     if (!a || !b || !out || n <= 0 || (n & 7)) return UR_E_BADARG;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const int64_t nvec = n / 8;
-    if (dtype == UR_DT_F16)
-        hipLaunchKernelGGL((add_kernel<f16>), dim3(grid_for(nvec)), dim3(256), 0, s, (const f16*)a, (const f16*)b, alpha,
-                           (f16*)out, nvec);
-    else if (dtype == UR_DT_BF16)
-        hipLaunchKernelGGL((add_kernel<bf16>), dim3(grid_for(nvec)), dim3(256), 0, s, (const bf16*)a, (const bf16*)b,
-                           alpha, (bf16*)out, nvec);
-    else
-        return UR_E_BADARG;
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : -(int)e;
+    UR_DISPATCH(dtype, hipLaunchKernelGGL((add_kernel<T>), dim3(grid_for(nvec, EW_BLOCKS)), dim3(256), 0, s, (const T*)a,
+                       (const T*)b, alpha, (T*)out, nvec));
+    return last_error();
 }
 
 template <typename T>
@@ -145,16 +133,9 @@ extern "C" int ur_add_hilo(const void* a, const void* a_lo, const void* b, const
     if (!a || !b || !out || n <= 0 || (n & 7)) return UR_E_BADARG;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const int64_t nvec = n / 8;
-    if (dtype == UR_DT_F16)
-        hipLaunchKernelGGL((add_hilo_kernel<f16>), dim3(grid_for(nvec)), dim3(256), 0, s, (const f16*)a, (const lo_t<f16>*)a_lo,
-                           (const f16*)b, (const lo_t<f16>*)b_lo, alpha, (f16*)out, (lo_t<f16>*)out_lo, nvec);
-    else if (dtype == UR_DT_BF16)
-        hipLaunchKernelGGL((add_hilo_kernel<bf16>), dim3(grid_for(nvec)), dim3(256), 0, s, (const bf16*)a,
-                           (const lo_t<bf16>*)a_lo, (const bf16*)b, (const lo_t<bf16>*)b_lo, alpha, (bf16*)out, (lo_t<bf16>*)out_lo, nvec);
-    else
-        return UR_E_BADARG;
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : -(int)e;
+    UR_DISPATCH(dtype, hipLaunchKernelGGL((add_hilo_kernel<T>), dim3(grid_for(nvec, EW_BLOCKS)), dim3(256), 0, s, (const T*)a,
+                       (const lo_t<T>*)a_lo, (const T*)b, (const lo_t<T>*)b_lo, alpha, (T*)out, (lo_t<T>*)out_lo, nvec));
+    return last_error();
 }
 
 // ur_add_hilo over up to UR_ADD_MULTI_MAX tensor triples in ONE launch: the 13 exchange adds of a sampling step whose
@@ -162,14 +143,12 @@ extern "C" int ur_add_hilo(const void* a, const void* a_lo, const void* b, const
 // in the kernel arguments; same per-element arithmetic as add_hilo_kernel with alpha = 1.
 struct AddMultiArgs {
     ur_add_item t[UR_ADD_MULTI_MAX];
-    int blk0[UR_ADD_MULTI_MAX + 1];
-    int n;
+    SegTable<UR_ADD_MULTI_MAX> seg;
 };
 
 template <typename T>
 __global__ void __launch_bounds__(256) add_hilo_multi_kernel(const AddMultiArgs a) {
-    int it = 0;
-    while (it + 1 < a.n && (int)blockIdx.x >= a.blk0[it + 1]) ++it;
+    const int it = a.seg.find(blockIdx.x);
     const ur_add_item e = a.t[it];
     const T* pa = (const T*)e.a;
     const T* pb = (const T*)e.b;
@@ -178,7 +157,7 @@ __global__ void __launch_bounds__(256) add_hilo_multi_kernel(const AddMultiArgs 
     T* po = (T*)e.out;
     lo_t<T>* lo = (lo_t<T>*)e.out_lo;
     const int64_t nvec = e.n / 8;
-    const int64_t v0 = (int64_t)((int)blockIdx.x - a.blk0[it]) * 1024;
+    const int64_t v0 = (int64_t)((int)blockIdx.x - a.seg.start[it]) * 1024;
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
         const int64_t i = v0 + u * 256 + threadIdx.x;
@@ -204,25 +183,15 @@ __global__ void __launch_bounds__(256) add_hilo_multi_kernel(const AddMultiArgs 
 }
 
 extern "C" int ur_add_hilo_multi(const ur_add_item* items, int n, int dtype, void* stream) {
-    if (!items || n <= 0 || n > UR_ADD_MULTI_MAX) return UR_E_BADARG;
     AddMultiArgs a;
-    int blocks = 0;
-    for (int i = 0; i < n; ++i) {
-        if (!items[i].a || !items[i].b || !items[i].out || items[i].n <= 0 || (items[i].n & 7)) return UR_E_BADARG;
-        a.t[i] = items[i];
-        a.blk0[i] = blocks;
-        const int64_t nb = (items[i].n / 8 + 1023) / 1024;
-        if (nb + blocks > (1 << 30)) return UR_E_UNSUPPORTED;
-        blocks += (int)nb;
-    }
-    a.blk0[n] = blocks;
-    a.n = n;
+    const int rc = pack(items, n, a.t, a.seg, UR_E_UNSUPPORTED, [](const ur_add_item& e) -> int64_t {
+        if (!e.a || !e.b || !e.out || e.n <= 0 || (e.n & 7)) return 0;
+        return (e.n / 8 + 1023) / 1024;
+    });
+    if (rc) return rc;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    if (dtype == UR_DT_F16) hipLaunchKernelGGL((add_hilo_multi_kernel<f16>), dim3(blocks), dim3(256), 0, s, a);
-    else if (dtype == UR_DT_BF16) hipLaunchKernelGGL((add_hilo_multi_kernel<bf16>), dim3(blocks), dim3(256), 0, s, a);
-    else return UR_E_BADARG;
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : -(int)e;
+    UR_DISPATCH(dtype, hipLaunchKernelGGL((add_hilo_multi_kernel<T>), dim3(a.seg.total()), dim3(256), 0, s, a));
+    return last_error();
 }
 extern "C" int ur_sizeof_add_item(void) { return (int)sizeof(ur_add_item); }
 
@@ -232,31 +201,17 @@ extern "C" int ur_timestep_embedding(const float* t, int nt, int B, int dim, int
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const int n = B * (dim / 2);
     dim3 grid((n + 255) / 256);
-    if (dtype == UR_DT_F16)
-        hipLaunchKernelGGL((timestep_kernel<f16>), grid, dim3(256), 0, s, t, nt, B, dim, flip_sin_to_cos, freq_shift,
-                           (f16*)out);
-    else if (dtype == UR_DT_BF16)
-        hipLaunchKernelGGL((timestep_kernel<bf16>), grid, dim3(256), 0, s, t, nt, B, dim, flip_sin_to_cos, freq_shift,
-                           (bf16*)out);
-    else
-        return UR_E_BADARG;
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : -(int)e;
+    UR_DISPATCH(dtype, hipLaunchKernelGGL((timestep_kernel<T>), grid, dim3(256), 0, s, t, nt, B, dim, flip_sin_to_cos,
+                       freq_shift, (T*)out));
+    return last_error();
 }
 
 template <typename S>
 static int to_nhwc_src(const void* src, int B, int C, int H, int W, void* dst, int Cpad, int dtype, hipStream_t s) {
     const int64_t total = (int64_t)B * H * W * Cpad;
-    if (dtype == UR_DT_F16)
-        hipLaunchKernelGGL((nchw_to_nhwc_kernel<S, f16>), dim3(grid_for(total)), dim3(256), 0, s, (const S*)src, B, C, H,
-                           W, (f16*)dst, Cpad);
-    else if (dtype == UR_DT_BF16)
-        hipLaunchKernelGGL((nchw_to_nhwc_kernel<S, bf16>), dim3(grid_for(total)), dim3(256), 0, s, (const S*)src, B, C, H,
-                           W, (bf16*)dst, Cpad);
-    else
-        return UR_E_BADARG;
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : -(int)e;
+    UR_DISPATCH(dtype, hipLaunchKernelGGL((nchw_to_nhwc_kernel<S, T>), dim3(grid_for(total, EW_BLOCKS)), dim3(256), 0, s,
+                       (const S*)src, B, C, H, W, (T*)dst, Cpad));
+    return last_error();
 }
 
 extern "C" int ur_resize_nearest(const void* in, void* out, int B, int Hin, int Win, int Hout, int Wout, int C, int dtype,
@@ -264,16 +219,9 @@ extern "C" int ur_resize_nearest(const void* in, void* out, int B, int Hin, int 
     if (!in || !out || B <= 0 || Hin <= 0 || Win <= 0 || Hout <= 0 || Wout <= 0 || C <= 0 || (C & 7)) return UR_E_BADARG;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const int64_t total = (int64_t)B * Hout * Wout * (C >> 3);
-    if (dtype == UR_DT_F16)
-        hipLaunchKernelGGL((resize_nearest_kernel<f16>), dim3(grid_for(total)), dim3(256), 0, s, (const f16*)in, (f16*)out, B,
-                           Hin, Win, Hout, Wout, C);
-    else if (dtype == UR_DT_BF16)
-        hipLaunchKernelGGL((resize_nearest_kernel<bf16>), dim3(grid_for(total)), dim3(256), 0, s, (const bf16*)in, (bf16*)out,
-                           B, Hin, Win, Hout, Wout, C);
-    else
-        return UR_E_BADARG;
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : -(int)e;
+    UR_DISPATCH(dtype, hipLaunchKernelGGL((resize_nearest_kernel<T>), dim3(grid_for(total, EW_BLOCKS)), dim3(256), 0, s,
+                       (const T*)in, (T*)out, B, Hin, Win, Hout, Wout, C));
+    return last_error();
 }
 
 extern "C" int ur_nchw_to_nhwc(const void* src, int src_dtype, int B, int C, int H, int W, void* dst, int Cpad,
@@ -288,29 +236,23 @@ extern "C" int ur_nchw_to_nhwc(const void* src, int src_dtype, int B, int C, int
 
 template <typename T>
 static int to_nchw_dst(const void* src, int B, int C, int H, int W, void* dst, int dst_dtype, hipStream_t s) {
-    const int64_t total = (int64_t)B * C * H * W;
+    const dim3 grid(grid_for((int64_t)B * C * H * W, EW_BLOCKS));
     if (dst_dtype == 0)
-        hipLaunchKernelGGL((nhwc_to_nchw_kernel<T, f16>), dim3(grid_for(total)), dim3(256), 0, s, (const T*)src, B, C, H,
-                           W, (f16*)dst);
+        hipLaunchKernelGGL((nhwc_to_nchw_kernel<T, f16>), grid, dim3(256), 0, s, (const T*)src, B, C, H, W, (f16*)dst);
     else if (dst_dtype == 1)
-        hipLaunchKernelGGL((nhwc_to_nchw_kernel<T, bf16>), dim3(grid_for(total)), dim3(256), 0, s, (const T*)src, B, C, H,
-                           W, (bf16*)dst);
+        hipLaunchKernelGGL((nhwc_to_nchw_kernel<T, bf16>), grid, dim3(256), 0, s, (const T*)src, B, C, H, W, (bf16*)dst);
     else if (dst_dtype == 2)
-        hipLaunchKernelGGL((nhwc_to_nchw_kernel<T, float>), dim3(grid_for(total)), dim3(256), 0, s, (const T*)src, B, C, H,
-                           W, (float*)dst);
+        hipLaunchKernelGGL((nhwc_to_nchw_kernel<T, float>), grid, dim3(256), 0, s, (const T*)src, B, C, H, W, (float*)dst);
     else
         return UR_E_BADARG;
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : -(int)e;
+    return last_error();
 }
 
 extern "C" int ur_nhwc_to_nchw(const void* src, int dtype, int B, int C, int H, int W, void* dst, int dst_dtype,
                                void* stream) {
     if (!src || !dst || B <= 0 || C <= 0 || H <= 0 || W <= 0) return UR_E_BADARG;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    if (dtype == UR_DT_F16) return to_nchw_dst<f16>(src, B, C, H, W, dst, dst_dtype, s);
-    if (dtype == UR_DT_BF16) return to_nchw_dst<bf16>(src, B, C, H, W, dst, dst_dtype, s);
-    return UR_E_BADARG;
+    UR_DISPATCH(dtype, return to_nchw_dst<T>(src, B, C, H, W, dst, dst_dtype, s));
 }
 
 // ------------------------------------------------------------------------------------------
@@ -429,18 +371,10 @@ extern "C" int ur_ddim_update(const void* pred, int pred_ld, int pred_c0, void* 
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const int64_t total = (int64_t)B * C * HW;
     const int grid = (int)((total + 255) / 256 > 2048 ? 2048 : (total + 255) / 256);
-    if (dtype == UR_DT_F16)
-        hipLaunchKernelGGL((ddim_update_kernel<f16>), dim3(grid), dim3(256), 0, s, (const f16*)pred, pred_ld, pred_c0,
-                           (f16*)lat, lat_bstride, C, B, HW, coef, step, nsteps, master, round_master, cfg, guidance,
-                           cfg_channels);
-    else if (dtype == UR_DT_BF16)
-        hipLaunchKernelGGL((ddim_update_kernel<bf16>), dim3(grid), dim3(256), 0, s, (const bf16*)pred, pred_ld, pred_c0,
-                           (bf16*)lat, lat_bstride, C, B, HW, coef, step, nsteps, master, round_master, cfg, guidance,
-                           cfg_channels);
-    else
-        return UR_E_BADARG;
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : -(int)e;
+    UR_DISPATCH(dtype, hipLaunchKernelGGL((ddim_update_kernel<T>), dim3(grid), dim3(256), 0, s, (const T*)pred, pred_ld,
+                       pred_c0, (T*)lat, lat_bstride, C, B, HW, coef, step, nsteps, master, round_master, cfg, guidance,
+                       cfg_channels));
+    return last_error();
 }
 
 extern "C" int ur_unipc_update(const void* pred, int pred_ld, int pred_c0, void* lat, int64_t lat_bstride, int C, int B,
@@ -453,26 +387,17 @@ extern "C" int ur_unipc_update(const void* pred, int pred_ld, int pred_c0, void*
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const int64_t total = (int64_t)B * C * HW;
     const int grid = (int)((total + 255) / 256 > 2048 ? 2048 : (total + 255) / 256);
-    if (dtype == UR_DT_F16)
-        hipLaunchKernelGGL((unipc_update_kernel<f16>), dim3(grid), dim3(256), 0, s, (const f16*)pred, pred_ld, pred_c0,
-                           (f16*)lat, lat_bstride, C, B, HW, coef, step, nsteps, last, xmaster, hist, round_master, cfg,
-                           guidance, cfg_channels);
-    else if (dtype == UR_DT_BF16)
-        hipLaunchKernelGGL((unipc_update_kernel<bf16>), dim3(grid), dim3(256), 0, s, (const bf16*)pred, pred_ld, pred_c0,
-                           (bf16*)lat, lat_bstride, C, B, HW, coef, step, nsteps, last, xmaster, hist, round_master, cfg,
-                           guidance, cfg_channels);
-    else
-        return UR_E_BADARG;
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : -(int)e;
+    UR_DISPATCH(dtype, hipLaunchKernelGGL((unipc_update_kernel<T>), dim3(grid), dim3(256), 0, s, (const T*)pred, pred_ld,
+                       pred_c0, (T*)lat, lat_bstride, C, B, HW, coef, step, nsteps, last, xmaster, hist, round_master, cfg,
+                       guidance, cfg_channels));
+    return last_error();
 }
 
 extern "C" int ur_sampler_advance(int* step, const float* tsteps, int nsteps, float* t_out, int B, void* stream) {
     if (!step || !tsteps || nsteps <= 0 || B < 0 || B > 256) return UR_E_BADARG;
     hipLaunchKernelGGL(sampler_advance_kernel, dim3(1), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), step, tsteps,
                        nsteps, t_out, B);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : -(int)e;
+    return last_error();
 }
 
 // dst[k][0..bytes_k) = src[k][*step][0..bytes_k) for up to 4 tables: the rows of the CURRENT step of per-step tables a sampling
@@ -504,8 +429,7 @@ extern "C" int ur_select_step_rows(const void* const* src, void* const* dst, con
     blocks = blocks < 1 ? 1 : (blocks > 64 ? 64 : blocks);
     hipLaunchKernelGGL(select_step_rows_kernel, dim3(blocks, ntab), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), a, ntab, step,
                        nsteps);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : -(int)e;
+    return last_error();
 }
 
 // One 4-byte load per 128-byte line, grid-strided; the value is consumed by an empty asm so the load is not dropped.
@@ -522,8 +446,7 @@ extern "C" int ur_prefetch(const void* ptr, int64_t bytes, int wgs, void* stream
     if (lines == 0) return 0;
     hipLaunchKernelGGL(prefetch_kernel, dim3(wgs), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
                        reinterpret_cast<const char*>(ptr), lines);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : -(int)e;
+    return last_error();
 }
 
 extern "C" int ur_abi_version(void) { return UR_ABI_VERSION; }

@@ -1,8 +1,7 @@
 // GroupNorm(+SiLU) over NHWC (optionally over the concat of two sources) and LayerNorm, gfx950.
 // Both are HBM-bound: 16-byte vector accesses, fp32 statistics, wave-shuffle / fixed-order LDS
 // reductions (deterministic: no floating-point atomics anywhere).
-#include "ur_common.h"
-#include "../../include/ur_kernels.h"
+#include "ur_launch.h"
 
 #include <cstdlib>
 
@@ -729,16 +728,10 @@ extern "C" int ur_groupnorm_stats(const void* x0, const void* x1, const void* x0
     if (rc || !partial) return rc ? rc : UR_E_BADARG;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     dim3 grid(nchunks, B);
-    if (dtype == UR_DT_F16)
-        hipLaunchKernelGGL((gn_stats_kernel<f16>), grid, dim3(256), 0, s, (const f16*)x0, (const f16*)x1,
-                           (const lo_t<f16>*)x0_lo, (const lo_t<f16>*)x1_lo, c0, c1, rows, groups, nchunks, partial, norm_xcd());
-    else if (dtype == UR_DT_BF16)
-        hipLaunchKernelGGL((gn_stats_kernel<bf16>), grid, dim3(256), 0, s, (const bf16*)x0, (const bf16*)x1,
-                           (const lo_t<bf16>*)x0_lo, (const lo_t<bf16>*)x1_lo, c0, c1, rows, groups, nchunks, partial, norm_xcd());
-    else
-        return UR_E_BADARG;
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : -(int)e;
+    UR_DISPATCH(dtype, hipLaunchKernelGGL((gn_stats_kernel<T>), grid, dim3(256), 0, s, (const T*)x0, (const T*)x1,
+                                          (const lo_t<T>*)x0_lo, (const lo_t<T>*)x1_lo, c0, c1, rows, groups, nchunks, partial,
+                                          norm_xcd()));
+    return last_error();
 }
 
 extern "C" int ur_groupnorm_apply(const void* x0, const void* x1, const void* x0_lo, const void* x1_lo, int c0, int c1,
@@ -749,18 +742,10 @@ extern "C" int ur_groupnorm_apply(const void* x0, const void* x1, const void* x0
     if (rc || nstat <= 0 || !partial || !gamma || !beta || !out) return rc ? rc : UR_E_BADARG;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     dim3 grid(nchunks, B);
-    if (dtype == UR_DT_F16)
-        hipLaunchKernelGGL((gn_apply_kernel<f16>), grid, dim3(256), 0, s, (const f16*)x0, (const f16*)x1,
-                           (const lo_t<f16>*)x0_lo, (const lo_t<f16>*)x1_lo, c0, c1, rows, groups, nstat, nchunks, partial, gamma, beta,
-                           eps, silu, bper, pstride, (f16*)out, norm_xcd());
-    else if (dtype == UR_DT_BF16)
-        hipLaunchKernelGGL((gn_apply_kernel<bf16>), grid, dim3(256), 0, s, (const bf16*)x0, (const bf16*)x1,
-                           (const lo_t<bf16>*)x0_lo, (const lo_t<bf16>*)x1_lo, c0, c1, rows, groups, nstat, nchunks, partial, gamma,
-                           beta, eps, silu, bper, pstride, (bf16*)out, norm_xcd());
-    else
-        return UR_E_BADARG;
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : -(int)e;
+    UR_DISPATCH(dtype, hipLaunchKernelGGL((gn_apply_kernel<T>), grid, dim3(256), 0, s, (const T*)x0, (const T*)x1,
+                                          (const lo_t<T>*)x0_lo, (const lo_t<T>*)x1_lo, c0, c1, rows, groups, nstat, nchunks,
+                                          partial, gamma, beta, eps, silu, bper, pstride, (T*)out, norm_xcd()));
+    return last_error();
 }
 
 // Which kernel ur_groupnorm_fused runs: the pieces-per-thread instantiation NP of gn_resident_kernel, or 0 = gn_fused_kernel
@@ -812,8 +797,7 @@ static int launch_gn_fused(const void* x0, const void* x1, const void* x0_lo, co
             else UR_GNR_P(2);
 #undef UR_GNR_P
 #undef UR_GNR
-            hipError_t e = hipGetLastError();
-            return e == hipSuccess ? 0 : -(int)e;
+            return last_error();
         }
     }
 #define UR_GNF(PP)                                                                                                     \
@@ -824,8 +808,7 @@ static int launch_gn_fused(const void* x0, const void* x1, const void* x0_lo, co
     else if (cpg % 2 == 0) UR_GNF(2);
     else return UR_E_UNSUPPORTED;
 #undef UR_GNF
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : -(int)e;
+    return last_error();
 }
 
 extern "C" int ur_groupnorm_fused(const void* x0, const void* x1, const void* x0_lo, const void* x1_lo, int c0, int c1,
@@ -834,11 +817,8 @@ extern "C" int ur_groupnorm_fused(const void* x0, const void* x1, const void* x0
     int rc = gn_check(x0, x1, c0, c1, B, rows, groups, 1);
     if (rc || !gamma || !beta || !out) return rc ? rc : UR_E_BADARG;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    if (dtype == UR_DT_F16)
-        return launch_gn_fused<f16>(x0, x1, x0_lo, x1_lo, c0, c1, B, rows, groups, gamma, beta, eps, silu, bper, pstride, out, s);
-    if (dtype == UR_DT_BF16)
-        return launch_gn_fused<bf16>(x0, x1, x0_lo, x1_lo, c0, c1, B, rows, groups, gamma, beta, eps, silu, bper, pstride, out, s);
-    return UR_E_BADARG;
+    UR_DISPATCH(dtype, return launch_gn_fused<T>(x0, x1, x0_lo, x1_lo, c0, c1, B, rows, groups, gamma, beta, eps, silu, bper,
+                                                 pstride, out, s));
 }
 
 template <typename T>
@@ -867,9 +847,6 @@ extern "C" int ur_layernorm(const void* x, const void* x_lo, const float* gamma,
                             int C, int rows_per_set, int pstride, void* out, int dtype, void* stream) {
     if (!x || !gamma || !beta || !out || rows <= 0 || C <= 0 || (C & 7) || C > 4096) return UR_E_BADARG;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    if (dtype == UR_DT_F16) launch_ln<f16>(x, x_lo, gamma, beta, eps, rows, C, rows_per_set, pstride, out, s);
-    else if (dtype == UR_DT_BF16) launch_ln<bf16>(x, x_lo, gamma, beta, eps, rows, C, rows_per_set, pstride, out, s);
-    else return UR_E_BADARG;
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : -(int)e;
+    UR_DISPATCH(dtype, launch_ln<T>(x, x_lo, gamma, beta, eps, rows, C, rows_per_set, pstride, out, s));
+    return last_error();
 }

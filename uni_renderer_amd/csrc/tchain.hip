@@ -21,9 +21,8 @@
 //
 // Global I/O happens only at the ends of a chain, 16 bytes per lane; the accumulator layout (4 consecutive channels per
 // register quad) is converted to / from 8 consecutive channels per lane with v_permlane32_swap.
-#include "ur_common.h"
+#include "ur_launch.h"
 #include <type_traits>
-#include "../../include/ur_kernels.h"
 #include "tchain_asm.inc"
 
 namespace ur {
@@ -597,8 +596,7 @@ static int launch_tchain(const ur_tchain_desc& d, hipStream_t s) {
     set_lds_limit_once(done, reinterpret_cast<const void*>(&tchain_kernel<T, MODE>), lds);
     const int tiles = (d.M + 127) / 128;
     hipLaunchKernelGGL((tchain_kernel<T, MODE>), dim3(tiles * d.zbatch), dim3(256), lds, s, d);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : -(int)e;
+    return last_error();
 }
 
 }  // namespace ur

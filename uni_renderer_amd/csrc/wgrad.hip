@@ -20,8 +20,7 @@
 //
 // Column sums of dy (the bias gradient) are taken from the dy fragments by the workgroups of k-tile 0: no separate launch.
 // Reference: the autograd of F.linear / F.conv2d under train/train.py:1416 (accelerator.backward).
-#include "ur_common.h"
-#include "../../include/ur_kernels.h"
+#include "ur_launch.h"
 
 namespace ur {
 
@@ -437,8 +436,7 @@ static int wgrad_launch_cfg(const WgradArgs& a, hipStream_t s) {
         const int blocks = (int)((total + 255) / 256 < 2048 ? (total + 255) / 256 : 2048);
         hipLaunchKernelGGL((wgrad_reduce<T>), dim3(blocks, a.n), dim3(256), 0, s, a);
     }
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : -(int)e;
+    return last_error();
 }
 
 template <typename T>
@@ -504,7 +502,7 @@ extern "C" int ur_wgrad_group(const ur_wgrad_desc* d, const ur_wgrad_ptrs* g, in
     a.n = n;
     for (int i = 0; i < n; ++i) a.g[i] = g[i];
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    return d->dtype == UR_DT_F16 ? ur::wgrad_launch<ur::f16>(a, s) : ur::wgrad_launch<ur::bf16>(a, s);
+    UR_DISPATCH(d->dtype, return ur::wgrad_launch<T>(a, s));
 }
 
 extern "C" int ur_wgrad_plan(const ur_wgrad_desc* d, int32_t* splits, int64_t* partial_floats) {

@@ -23,9 +23,8 @@
 //
 // LDS: 2 x 40960 (weights) + 4 x 20480 (operand staging) = the whole 160 KiB; constants are read from global memory in
 // the epilogue.
-#include "ur_common.h"
+#include "ur_launch.h"
 #include <type_traits>
-#include "../../include/ur_kernels.h"
 #include "tchain_asm.inc"
 
 namespace ur {
@@ -741,8 +740,7 @@ static int launch_ws(const ur_igemm_desc& d, hipStream_t s, bool half) {
         set_lds_limit_once(donebf, reinterpret_cast<const void*>(&wsconv_kernel_bf16), WS_LDS);
         hipLaunchKernelGGL(wsconv_kernel_bf16, dim3(wgs), dim3(256), WS_LDS, s, d);
     }
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : -(int)e;
+    return last_error();
 }
 
 // main pass only: the caller (igemm.hip) runs igemm_splitk_reduce behind it when d.splitk > 1

@@ -878,20 +878,19 @@ def add_multi(pairs, hilo=False):
     if not pairs:
         return []
     _require_gpu(pairs[0][0])
-    lib = _lib.load()
     outs = [_with_lo(torch.empty_like(a), hilo) for a, _ in pairs]
     dt = pairs[0][0].dtype
     e0 = _prof_begin()
-    for i in range(0, len(pairs), ADD_MULTI_MAX):
-        chunk = pairs[i:i + ADD_MULTI_MAX]
-        arr = (_AddItem * len(chunk))()
-        for k, (a, b) in enumerate(chunk):
-            if a.dtype != dt or b.dtype != dt or a.shape != b.shape or not (a.is_contiguous() and b.is_contiguous()):
-                raise RuntimeError("add_multi: operands of one pair must be contiguous tensors of one shape and dtype")
-            o = outs[i + k]
-            arr[k].a, arr[k].a_lo, arr[k].b, arr[k].b_lo = a.data_ptr(), _ptr(lo_of(a)), b.data_ptr(), _ptr(lo_of(b))
-            arr[k].out, arr[k].out_lo, arr[k].n = o.data_ptr(), _ptr(lo_of(o)), a.numel()
-        check(lib.ur_add_hilo_multi(arr, len(chunk), DT[dt], _stream()), "ur_add_hilo_multi")
+
+    def fill(d, pair, i):
+        a, b = pair
+        if a.dtype != dt or b.dtype != dt or a.shape != b.shape or not (a.is_contiguous() and b.is_contiguous()):
+            raise RuntimeError("add_multi: operands of one pair must be contiguous tensors of one shape and dtype")
+        o = outs[i]
+        d.a, d.a_lo, d.b, d.b_lo = a.data_ptr(), _ptr(lo_of(a)), b.data_ptr(), _ptr(lo_of(b))
+        d.out, d.out_lo, d.n = o.data_ptr(), _ptr(lo_of(o)), a.numel()
+
+    _lib.launch_chunked("ur_add_hilo_multi", _AddItem, pairs, ADD_MULTI_MAX, fill, DT[dt], _stream())
     _prof_end(e0, "add_multi", 0.0, sum(3.0 * o.numel() * o.element_size() for o in outs))
     return outs
 

@@ -117,16 +117,12 @@ class FusedAdamW(torch.optim.Optimizer):
                 if st["step"] is not step_t:
                     st["step"] = step_t
             step_t += 1
-            arrays = []
-            for i in range(0, len(ps), MAX_TENSORS):
-                chunk = ps[i:i + MAX_TENSORS]
-                arr = (_Tensor * len(chunk))()
-                for k, p in enumerate(chunk):
-                    st = states[i + k]
-                    arr[k].p, arr[k].g = p.data_ptr(), p.grad.data_ptr()
-                    arr[k].m, arr[k].v = st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr()
-                    arr[k].n = p.numel()
-                arrays.append(arr)
+
+            def fill(d, p, i):
+                d.p, d.g, d.n = p.data_ptr(), p.grad.data_ptr(), p.numel()
+                d.m, d.v = states[i]["exp_avg"].data_ptr(), states[i]["exp_avg_sq"].data_ptr()
+
+            arrays = _lib.desc_arrays(_Tensor, ps, MAX_TENSORS, fill)
             # the cache holds raw addresses: keep what they point into alive next to it (states live in self.state)
             group["_ur_launches"] = (gptrs, tuple(p.data_ptr() for p in ps), arrays, step_t)
             self._launch(lib, group, arrays, step_t, grad_scale, found_inf)
