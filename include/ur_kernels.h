@@ -49,9 +49,10 @@ extern "C" {
 /* This header is the ONE description of the ABI: the Python binding (uni_renderer_amd/_lib.py) reads it at import and derives
  * every prototype, struct mirror and integer constant from it, and checks the loaded library against it (this version, and
  * every ur_sizeof_X() against struct ur_X).  So it is written in the few shapes that reader accepts -- `#define UR_NAME
- * <integer>`; structs of pointers, int32_t / int64_t / int / float and char[N] fields; functions of int / int32_t / int64_t /
+ * <integer>`; structs of pointers (to void / float / int / uint8_t / uint32_t / int32_t / int64_t), int32_t / int64_t / int / float and
+ * char[N] fields; functions of int / int32_t / int64_t /
  * float and pointer parameters that return int, int64_t or const char* -- and no field is named like a Python keyword. */
-#define UR_ABI_VERSION 16
+#define UR_ABI_VERSION 17
 
 #define UR_E_BADARG (-1001)   /* inconsistent descriptor (shape / alignment / null pointer)   */
 #define UR_E_UNSUPPORTED (-1002) /* shape outside what the kernels are instantiated for       */
@@ -622,6 +623,31 @@ typedef struct ur_adamw_tensor {
 int ur_adamw_multi(const ur_adamw_tensor* tensors, int n_tensors, float lr, float beta1, float beta2, float eps,
                    float weight_decay, const float* step, const float* grad_scale, const float* found_inf,
                    const float* hyper, void* stream);
+
+/* AdamW with block-wise dynamic 8-bit moments (ABI 17; Dettmers et al., arXiv 2110.02861 -- what the reference selects with
+ * --use_8bit_adam, train/train.py:1101-1128).  A block is 256 consecutive elements of one tensor (the last may be partial)
+ * and owns one fp32 absmax per moment; a moment is stored as the index (one byte) of the entry of a 256-entry code book
+ * nearest to value / absmax and read back as book[code] * absmax.  exp_avg uses the signed book (zero = code 127), exp_avg_sq
+ * the unsigned one (zero = code 0).  Two deliberate rules: a block whose absmax is 0 stores the zero code without dividing,
+ * and a strictly positive exp_avg_sq never stores code 0 but code 1 (an exp_avg_sq rounded to 0 makes the next small
+ * gradient divide by eps alone).  Fresh state: codes 127 / 0, absmax 0.
+ * One step per block: decode m and v, then exactly the arithmetic and arguments of ur_adamw_multi (the parameter is updated
+ * from the fresh fp32 moments), then the block maxima of the fresh moments, encode, store codes and both absmax.  found_inf
+ * != 0 leaves every byte untouched.  m, v: [n] codes; absmax_m, absmax_v: [ceil(n / 256)] fp32.  Tensors whose p / g are
+ * 16-byte and whose codes are 4-byte aligned take the vector path.  No atomics, fixed reduction order.
+ * items: a HOST table of seven int64_t words per tensor, [n_tensors][7] = { p, g, m, v, absmax_m, absmax_v, n }: six device
+ * addresses (float* p, const float* g, uint8_t* m, uint8_t* v, float* absmax_m, float* absmax_v) and the element count.  Up to
+ * UR_ADAMW_MAX_TENSORS tensors per launch; the checks and return codes of ur_adamw_multi (a null address or n <= 0 in any
+ * row: UR_E_BADARG). */
+int ur_adamw8_multi(const int64_t* items, int n_tensors, float lr, float beta1, float beta2, float eps,
+                    float weight_decay, const float* step, const float* grad_scale, const float* found_inf,
+                    const float* hyper, void* stream);
+/* The same encode / decode on their own (state import and export): x [n] fp32 <-> codes [n], absmax [ceil(n / 256)].
+ * is_signed: 1 = the exp_avg book, 0 = the exp_avg_sq book (with its code-1 rule). */
+int ur_adam8_quantize(const float* x, uint8_t* codes, float* absmax, int64_t n, int is_signed, void* stream);
+int ur_adam8_dequantize(float* x, const uint8_t* codes, const float* absmax, int64_t n, int is_signed, void* stream);
+/* Host only: copies the 256 ascending fp32 entries of a code book into HOST memory out256. */
+int ur_adam8_codebook(int is_signed, float* out256);
 
 /* Flash backward of o = softmax(q k^T * scale) v (ur_attention_backward_supported: Tq % 64 == 0, d % 8 == 0, d <= 160).
  * Replaces the reference's autograd through F.scaled_dot_product_attention (diffusers AttnProcessor2_0 under

@@ -40,7 +40,10 @@ def main():
                     help="gradient collective per bucket: one all-reduce, or reduce-scatter + all-gather (all 7 xGMI links)")
     ap.add_argument("--comm-dtype", default="bf16", choices=["bf16", "fp32"])
     ap.add_argument("--no-overlap", action="store_true", help="reduce all buckets after the backward instead of during it")
-    ap.add_argument("--torch-adamw", action="store_true", help="torch.optim.AdamW(fused=True) instead of optim.FusedAdamW")
+    which = ap.add_mutually_exclusive_group()
+    which.add_argument("--torch-adamw", action="store_true", help="torch.optim.AdamW(fused=True) instead of optim.FusedAdamW")
+    which.add_argument("--adamw8bit", action="store_true", help="optim.AdamW8bit (block-wise 8-bit moments, train.py --use_8bit_adam) "
+                       "instead of optim.FusedAdamW")
     ap.add_argument("--gpus", type=int, default=0, help="without a launcher: start this many ranks (one per GPU) ourselves")
     ap.add_argument("--graph", action="store_true", help="time HIP-graph replays (train_step.GraphedTrainStep): one GPU = the whole step "
                     "as one graph; several = ONE graph with the bucket collectives captured as parallel branches (overlapped "
@@ -79,6 +82,9 @@ def main():
     params = [p for m in nets for p in m.parameters()]
     if args.torch_adamw:
         opt = torch.optim.AdamW(params, lr=1e-5, fused=True, capturable=args.graph)
+    elif args.adamw8bit:
+        from uni_renderer_amd.optim import AdamW8bit
+        opt = AdamW8bit(params, lr=1e-5)
     else:
         from uni_renderer_amd.optim import FusedAdamW
         opt = FusedAdamW(params, lr=1e-5)

@@ -11,6 +11,9 @@ Interchangeable with ``torch.optim.AdamW``: same constructor arguments, ``param_
 ``grad_scale`` / ``found_inf`` attributes of torch's AMP-aware fused optimizers (train_step.py folds gradient clipping
 into the update through ``grad_scale``), and no host synchronisation in ``step()`` (the step counter is a device
 scalar): the whole training step still captures into one HIP graph.
+
+``AdamW8bit`` (below) is the reference's other choice, ``--use_8bit_adam`` (train/train.py:1101-1128): the same optimizer with
+block-wise 8-bit moments on ``ur_adamw8_multi`` (csrc/adamw8.hip).
 """
 from __future__ import annotations
 
@@ -24,6 +27,19 @@ from .ops import _stream
 
 MAX_TENSORS = ABI.UR_ADAMW_MAX_TENSORS
 _Tensor = _lib.STRUCTS["ur_adamw_tensor"]
+BLOCK_8BIT = 256  # elements per absmax of the 8-bit state (csrc/adamw8.hip)
+
+
+def adamw8_tables(rows) -> list:
+    """The item tables of ``ur_adamw8_multi`` over ``rows`` of (p, g, m, v, absmax_m, absmax_v, n) -- six device addresses and
+    the element count: one ctypes ``int64_t [k][7]`` array and its k per ``MAX_TENSORS`` rows."""
+    import ctypes
+
+    tables = []
+    for i in range(0, len(rows), MAX_TENSORS):
+        part = rows[i:i + MAX_TENSORS]
+        tables.append(((ctypes.c_int64 * (7 * len(part)))(*(int(w) for row in part for w in row)), len(part)))
+    return tables
 
 
 class FusedAdamW(torch.optim.Optimizer):
@@ -217,3 +233,236 @@ class FusedAdamW(torch.optim.Optimizer):
                 group["_ur_launches"] = old_launch[gi]  # same addresses: the descriptor arrays are still right
         if replaced:
             self.generation = getattr(self, "generation", 0) + 1
+
+
+# ---------------------------------------------------------------------------------------------
+# block-wise 8-bit state (ur_adamw8_multi, csrc/adamw8.hip)
+# ---------------------------------------------------------------------------------------------
+_MOMENTS = (("exp_avg", "exp_avg_absmax", 1), ("exp_avg_sq", "exp_avg_sq_absmax", 0))  # codes, block maxima, signed book?
+
+
+def codebook(signed: bool) -> torch.Tensor:
+    """The library's 256-entry fp32 code book (``ur_adam8_codebook``): ``signed`` for exp_avg, unsigned for exp_avg_sq."""
+    import ctypes
+
+    out = (ctypes.c_float * 256)()
+    check(_lib.load().ur_adam8_codebook(int(bool(signed)), out), "ur_adam8_codebook")
+    return torch.tensor(list(out), dtype=torch.float32)
+
+
+def quantize_blockwise(x: torch.Tensor, signed: bool, codes: torch.Tensor = None, absmax: torch.Tensor = None):
+    """``(codes, absmax)`` of the fp32 GPU tensor ``x`` (``ur_adam8_quantize``): uint8 of x's shape and fp32 [ceil(n / 256)],
+    written into ``codes`` / ``absmax`` when given."""
+    if not x.is_cuda or x.dtype != torch.float32 or not x.is_contiguous() or x.numel() == 0:
+        raise RuntimeError("quantize_blockwise needs a non-empty contiguous fp32 tensor on the GPU")
+    n = x.numel()
+    if codes is None:
+        codes = torch.empty(x.shape, dtype=torch.uint8, device=x.device)
+    if absmax is None:
+        absmax = torch.empty(-(-n // BLOCK_8BIT), dtype=torch.float32, device=x.device)
+    check(_lib.load().ur_adam8_quantize(x.data_ptr(), codes.data_ptr(), absmax.data_ptr(), n, int(bool(signed)), _stream()),
+          "ur_adam8_quantize")
+    return codes, absmax
+
+
+def dequantize_blockwise(codes: torch.Tensor, absmax: torch.Tensor, signed: bool) -> torch.Tensor:
+    """fp32 ``book[codes] * absmax`` of the GPU tensors ``codes`` (uint8) / ``absmax`` (``ur_adam8_dequantize``)."""
+    n = codes.numel()
+    if (not codes.is_cuda or codes.dtype != torch.uint8 or not codes.is_contiguous() or n == 0 or absmax.dtype != torch.float32
+            or absmax.device != codes.device or not absmax.is_contiguous() or absmax.numel() != -(-n // BLOCK_8BIT)):
+        raise RuntimeError("dequantize_blockwise needs contiguous uint8 codes and fp32 [ceil(n / 256)] block maxima on the GPU")
+    x = torch.empty(codes.shape, dtype=torch.float32, device=codes.device)
+    check(_lib.load().ur_adam8_dequantize(x.data_ptr(), codes.data_ptr(), absmax.data_ptr(), n, int(bool(signed)), _stream()),
+          "ur_adam8_dequantize")
+    return x
+
+
+class AdamW8bit(FusedAdamW):
+    """``FusedAdamW`` with block-wise dynamic 8-bit moments (Dettmers et al., arXiv 2110.02861): what the reference's
+    ``--use_8bit_adam`` selects (``bnb.optim.AdamW8bit``, train/train.py:1101-1128).  Tensors of at least ``min_8bit_size``
+    elements keep ``exp_avg`` / ``exp_avg_sq`` as one byte per element plus one fp32 block maximum per 256 elements and moment
+    (2 n + 8 ceil(n / 256) bytes instead of 8 n) and are updated by ``ur_adamw8_multi``; smaller ones (biases, norm vectors)
+    keep fp32 state and go through ``ur_adamw_multi`` bit-for-bit as in ``FusedAdamW``.  Everything else is ``FusedAdamW``:
+    one device step counter per group, lr / weight decay in device memory, ``grad_scale`` / ``found_inf``, no host
+    synchronisation in ``step()``, in-place ``load_state_dict``.
+
+    The scheme is restated in include/ur_kernels.h, not taken from bitsandbytes: parity with bitsandbytes is unpinned, and a
+    strictly positive ``exp_avg_sq`` never rounds to zero (code 1 instead), which the published scheme does not say.  8-bit
+    state is not a numerical drop-in for fp32 AdamW (DESIGN.md has the measured distance).
+
+    ``state_dict()``: per parameter ``step``, ``exp_avg`` / ``exp_avg_sq`` as uint8 tensors of the parameter's shape and
+    ``exp_avg_absmax`` / ``exp_avg_sq_absmax`` as fp32 [ceil(n / 256)]; small tensors as in torch.  ``load_state_dict`` takes
+    that or torch's fp32 layout (quantised on load); ``dequantized_state_dict()`` hands out torch's layout."""
+
+    def __init__(self, params: Iterable, lr: float = 1e-3, betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-8,
+                 weight_decay: float = 1e-2, min_8bit_size: int = 4096, amsgrad: bool = False, percentile_clipping: int = 100,
+                 block_wise: bool = True):
+        # the switches of bnb.optim.AdamW8bit that change the arithmetic: accepted at their defaults only
+        if amsgrad or percentile_clipping != 100 or not block_wise:
+            raise NotImplementedError("AdamW8bit: amsgrad, percentile_clipping != 100 and block_wise=False are not implemented")
+        if min_8bit_size < 0:
+            raise ValueError("invalid min_8bit_size")
+        self.min_8bit_size = int(min_8bit_size)
+        super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
+
+    def _is_8bit(self, p) -> bool:
+        return p.numel() >= self.min_8bit_size and p.numel() > 0
+
+    def _init_state(self, p):
+        if not self._is_8bit(p):
+            return super()._init_state(p)
+        st = self.state[p]
+        if not st:
+            nblk = -(-p.numel() // BLOCK_8BIT)
+            st["step"] = torch.zeros((), dtype=torch.float32, device=p.device)
+            st["exp_avg"] = torch.full(p.shape, 127, dtype=torch.uint8, device=p.device)  # the signed book's zero
+            st["exp_avg_sq"] = torch.zeros(p.shape, dtype=torch.uint8, device=p.device)
+            st["exp_avg_absmax"] = torch.zeros(nblk, dtype=torch.float32, device=p.device)
+            st["exp_avg_sq_absmax"] = torch.zeros(nblk, dtype=torch.float32, device=p.device)
+        return st
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        lib = _lib.load()
+        grad_scale = getattr(self, "grad_scale", None)
+        found_inf = getattr(self, "found_inf", None)
+        if not torch.cuda.is_current_stream_capturing():
+            self.sync_hyper()
+        for group in self.param_groups:
+            if group.get("amsgrad") or group.get("maximize"):
+                raise NotImplementedError("AdamW8bit: amsgrad / maximize are not used by the reference (train.py:1101-1128)")
+            ps = [p for p in group["params"] if p.grad is not None]
+            if not ps:
+                continue
+            gptrs = tuple(p.grad.data_ptr() for p in ps)
+            cached = group.get("_ur_launches")
+            if cached is None or cached[0] != gptrs or cached[1] != tuple(p.data_ptr() for p in ps):
+                for p in ps:
+                    if p.dtype != torch.float32 or p.grad.dtype != torch.float32 or not p.is_cuda:
+                        raise RuntimeError("AdamW8bit updates fp32 master parameters on the GPU (train.py:1082-1089)")
+                    if not p.is_contiguous() or not p.grad.is_contiguous():
+                        raise RuntimeError("AdamW8bit needs contiguous parameters and gradients")
+                states = {p: self._init_state(p) for p in ps}
+                step_t = states[ps[0]]["step"]  # one device step counter per group, shared by both kinds of tensor
+                for st in states.values():
+                    if st["step"] is not step_t:
+                        st["step"] = step_t
+                big = [p for p in ps if self._is_8bit(p)]
+                small = [p for p in ps if not self._is_8bit(p)]
+
+                def row8(p):
+                    st = states[p]
+                    return (p.data_ptr(), p.grad.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(),
+                            st["exp_avg_absmax"].data_ptr(), st["exp_avg_sq_absmax"].data_ptr(), p.numel())
+
+                def fill(d, p, i):
+                    d.p, d.g, d.n = p.data_ptr(), p.grad.data_ptr(), p.numel()
+                    d.m, d.v = states[p]["exp_avg"].data_ptr(), states[p]["exp_avg_sq"].data_ptr()
+
+                cached = group["_ur_launches"] = (gptrs, tuple(p.data_ptr() for p in ps), _lib.desc_arrays(_Tensor, small, MAX_TENSORS, fill),
+                                                  step_t, adamw8_tables([row8(p) for p in big]))
+            step_t = cached[3]
+            step_t += 1
+            beta1, beta2 = group["betas"]
+            hy = group.get("_ur_hyper")
+            if hy is None:
+                raise RuntimeError("AdamW8bit.step() inside a graph capture before any eager step: call sync_hyper() first")
+            for table, count in cached[4]:
+                check(lib.ur_adamw8_multi(table, count, float(group["lr"]), float(beta1), float(beta2), float(group["eps"]),
+                                          float(group["weight_decay"]), step_t.data_ptr(),
+                                          grad_scale.data_ptr() if grad_scale is not None else None,
+                                          found_inf.data_ptr() if found_inf is not None else None, hy[0].data_ptr(), _stream()),
+                      "ur_adamw8_multi")
+            # the fp32 tensors, and the step counter's correction after a skipped step, exactly as FusedAdamW
+            self._launch(lib, group, cached[2], step_t, grad_scale, found_inf)
+        return loss
+
+    def dequantized_state_dict(self):
+        """``state_dict()`` in torch.optim.AdamW's layout (fp32 ``exp_avg`` / ``exp_avg_sq``, no block maxima): loads into
+        ``FusedAdamW`` or ``torch.optim.AdamW``."""
+        sd = self.state_dict()
+        for st in sd["state"].values():
+            for key, amax, signed in _MOMENTS:
+                if amax in st:
+                    st[key] = dequantize_blockwise(st[key], st.pop(amax), signed)
+        return sd
+
+    def load_state_dict(self, state_dict):
+        """As ``FusedAdamW.load_state_dict`` (in place wherever the live state has the loaded shapes, ``generation`` bumped
+        otherwise), for this class's layout and for torch's: fp32 moments of an 8-bit tensor are quantised on the way in, and
+        codes of a tensor that is below ``min_8bit_size`` here are decoded."""
+        old_hyper = [g.get("_ur_hyper") for g in self.param_groups]
+        old_launch = [g.get("_ur_launches") for g in self.param_groups]
+        old_state = {p: dict(self.state[p]) for g in self.param_groups for p in g["params"] if self.state.get(p)}
+        # torch casts every state tensor to the parameter's dtype (uint8 codes would come back as fp32, and fp32 moments of
+        # the whole model would be resident at once): it gets the step counters only, the moments are placed below
+        keys = {k for m in _MOMENTS for k in m[:2]}
+        moments = {pid: {k: v for k, v in st.items() if k in keys} for pid, st in state_dict["state"].items()}
+        torch.optim.Optimizer.load_state_dict(self, {
+            "state": {pid: {k: v for k, v in st.items() if k not in keys} for pid, st in state_dict["state"].items()},
+            "param_groups": state_dict["param_groups"]})
+        replaced = False
+        for gi, (group, saved) in enumerate(zip(self.param_groups, state_dict["param_groups"])):
+            group.pop("_ur_launches", None)
+            group.pop("_ur_hyper", None)
+            hy = old_hyper[gi] if gi < len(old_hyper) else None
+            if hy is not None:
+                hy[1] = None  # same device pair, value re-sent by the next sync_hyper()
+                group["_ur_hyper"] = hy
+            step_t = None
+            for p, pid in zip(group["params"], saved["params"]):
+                st, prev, mom = self.state.get(p), old_state.get(p), moments.get(pid, {})
+                want = [k for m in _MOMENTS for k in (m[:2] if self._is_8bit(p) else m[:1])]
+                if prev is not None and not ("step" in (st or {}) and "exp_avg" in mom and "exp_avg_sq" in mom):
+                    replaced = True  # live state that the loaded dict lacks: its addresses are gone (see FusedAdamW)
+                if not st and not mom:
+                    continue
+                st = self.state[p]
+                if "exp_avg" in mom and "exp_avg_sq" in mom:
+                    new = self._convert(p, mom)
+                    for k in want:
+                        if prev is not None and k in prev and prev[k].shape == new[k].shape and prev[k].dtype == new[k].dtype:
+                            prev[k].copy_(new[k])
+                            st[k] = prev[k]
+                        else:
+                            st[k] = new[k] if new[k].device == p.device and new[k] is not mom.get(k) else new[k].to(p.device, copy=True)
+                            replaced = True
+                if "step" in st:
+                    new = torch.as_tensor(st["step"], dtype=torch.float32).to(p.device).reshape(())
+                    if prev is not None and "step" in prev:
+                        if step_t is None or prev["step"] is not step_t:
+                            prev["step"].copy_(new)
+                        st["step"] = step_t = prev["step"]  # the group's one device counter keeps its address
+                    else:
+                        st["step"] = new.clone()
+                        replaced = True
+            if not replaced and gi < len(old_launch) and old_launch[gi] is not None:
+                group["_ur_launches"] = old_launch[gi]  # same addresses: the descriptor arrays are still right
+        if replaced:
+            self.generation = getattr(self, "generation", 0) + 1
+
+    def _convert(self, p, mom):
+        """The loaded moments ``mom`` of parameter ``p`` in the layout ``p`` has here: codes + block maxima (8-bit tensors) or
+        fp32 (small ones).  Tensors already in that layout pass through untouched, on whatever device they are."""
+        out = {}
+        for key, amax, signed in _MOMENTS:
+            t = mom[key]
+            coded = amax in mom
+            if coded and (t.dtype != torch.uint8 or mom[amax].numel() != -(-t.numel() // BLOCK_8BIT)):
+                raise ValueError(f"AdamW8bit.load_state_dict: {key} has block maxima but is not a uint8 code tensor of their size")
+            if t.shape != p.shape:
+                raise ValueError(f"AdamW8bit.load_state_dict: {key} of shape {tuple(t.shape)} for a parameter of shape {tuple(p.shape)}")
+            if self._is_8bit(p):
+                if coded:
+                    out[key], out[amax] = t, mom[amax].to(torch.float32)
+                else:
+                    out[key], out[amax] = quantize_blockwise(t.to(p.device, torch.float32).contiguous(), signed)
+            elif coded:
+                out[key] = dequantize_blockwise(t.to(p.device).contiguous(), mom[amax].to(p.device, torch.float32).contiguous(), signed)
+            else:
+                out[key] = t.to(torch.float32)
+        return out
