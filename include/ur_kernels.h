@@ -372,6 +372,31 @@ int ur_add_hilo(const void* a, const void* a_lo, const void* b, const void* b_lo
 int ur_freeu(void* hidden, void* hidden_lo, int Ch, float b, const void* skip, const void* skip_lo, void* skip_out,
              void* skip_out_lo, int Cs, float s, int B, int H, int W, int dtype, void* stream);
 
+/*
+ * Direct 3x3 convolution, pad 1, stride 1 | 2, for maps with FEW channels (csrc/condconv.hip): the seven narrow layers of the
+ * ControlNet conditioning embedding (reference models/controlnet.py, `controlnet_cond_embedding`: 3 -> 16 -> 16 -> 32 -> 32 ->
+ * 96 -> 96 -> 256 channels with SiLU between them), which the 64-channel K granularity of the implicit GEMM would pad 4x.  An
+ * ADDITION to ABI 17: no existing symbol, struct or constant changes, so the version number stays.
+ *   out[b][oy][ox][n] = act( bias[n] + sum over (ky, kx, c) of x[b][oy * stride - 1 + ky][ox * stride - 1 + kx][c] * W[n][c][ky][kx] )
+ *   x       x_nchw == 0: NHWC [B][H][W][Cin] in `dtype` (x_dtype == dtype), Cin a multiple of 16, at most 256.
+ *           x_nchw == 1 (image mode): the caller's contiguous NCHW image [B][Cin][H][W], Cin = 1 .. 4, x_dtype = UR_DT_F16 /
+ *           BF16 / F32; every element is rounded to `dtype` first, K is padded inside the kernel.
+ *   out     NHWC [B][Ho][Wo][Cout] in `dtype`, Ho = (H - 1) / stride + 1, Wo likewise; Cout a multiple of 16, at most 256.
+ *   bias    [Cout] fp32.   act: UR_ACT_NONE or UR_ACT_SILU.   fp32 accumulation in a fixed order, one rounding to `dtype`.
+ *   w       the packed weights, in `dtype`: with CC = the k chunk that the second function names for (Cin, stride, x_nchw) -- 8,
+ *           16 or 32 input channels -- Cp = Cin rounded up to CC and STEPS = ceil(9 * CC / 32), the image is
+ *           [Cout / 16][Cp / CC][STEPS][64][8]: element j of lane l of step s of chunk q of block nb is
+ *           W[nb * 16 + l % 16][q * CC + k % CC][tap / 3][tap % 3] with k = 32 * s + 8 * (l / 16) + j and tap = k / CC, and zero
+ *           where tap >= 9 or the channel is >= Cin.  A `bgr` image is a flip of the channel axis of W at pack time.
+ * Out-of-image taps read zeros; a halo never reads the neighbouring sample.  Offsets are 64-bit.  Null pointers, sizes <= 0,
+ * x / w / bias / out not 16-byte aligned (image mode: x not element aligned), an unknown dtype or act: UR_E_BADARG.  Any other
+ * stride, Cin or Cout: UR_E_UNSUPPORTED.  Both before any launch.
+ */
+int ur_cond_conv3x3(const void* x, int x_dtype, int x_nchw, const void* w, const float* bias, void* out, int B, int H, int W,
+                    int Cin, int Cout, int stride, int act, int dtype, void* stream);
+/* Host only: the k chunk CC (8, 16 or 32) of the weight image above, or UR_E_UNSUPPORTED for a stride / Cin the kernel refuses. */
+int ur_cond_conv3x3_kchunk(int Cin, int stride, int x_nchw);
+
 /* ur_add_hilo (alpha = 1) over up to UR_ADD_MULTI_MAX independent tensor triples in ONE launch (ABI 10).  What a sampling
  * loop with a loop-invariant exchange operand runs per step instead of 13 exchange GEMMs: in the inverse-rendering loop
  * (models/pipeline.py:2629-2690) the UNet's skips are constant, so `control_down_blocks[i](skip_unet[i])`

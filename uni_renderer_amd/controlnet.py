@@ -3,6 +3,7 @@
   ``UNet2DConditionModel``   image stream            (ref 49-1166;  forward 781-1166)
   ``AttributeEncoderModel``  attribute stream, down  (ref 1170-1778; forward 1657-1778; from_unet 1437-1507)
   ``AttributeDecoderModel``  attribute stream, up    (ref 1781-2527; forward 2342-2527; from_unet 2115-2192)
+  ``ControlNetModel``        control by an image     (ref 2530-3266; forward 3065-3266; from_unet 2848-2915)
 
 Same class names, constructor keywords, ``forward`` signatures, return conventions and ``state_dict`` keys as
 the reference, so ``train/train.py:1324-1354`` / ``models/pipeline.py:2660-2690`` call them unchanged.  Inside,
@@ -24,8 +25,8 @@ import torch
 import torch.nn as nn
 
 from . import ops
-from .layers import Attention, Conv2d, Ctx, GroupNorm, PackCache, ResnetBlock2D, TimestepEmbedding, f32, pack_conv3x3, \
-    pack_matrix, zero_module
+from .layers import Attention, ControlNetConditioningEmbedding, Conv2d, Ctx, GroupNorm, PackCache, ResnetBlock2D, \
+    TimestepEmbedding, f32, pack_conv3x3, pack_matrix, zero_module
 from .modeling_utils import ConfigModelMixin, register_to_config
 from .unet_2d_blocks import FREEU_KEYS, UNetMidBlock2DCrossAttn, freeu_enabled, get_down_block, get_up_block
 
@@ -143,13 +144,16 @@ class _DenoiserBase(ConfigModelMixin, nn.Module):
             ehs = ehs.to(dt).contiguous()  # boundary cast of the [B,77,768] prompt embedding (plumbing)
         return ehs
 
-    def _conv_in(self, x_nchw: torch.Tensor, ctx: Ctx) -> torch.Tensor:
+    def _conv_in(self, x_nchw: torch.Tensor, ctx: Ctx, res=None) -> torch.Tensor:
+        """``res``: an NHWC tensor added in the conv's epilogue (one launch, one rounding)."""
         dt = ctx.dtype
         w = self._pk.get("cin_w", [self.conv_in.weight], dt, lambda: pack_conv3x3(self.conv_in.weight, dt, CIN_PAD))
         b = self._pk.get("cin_b", [self.conv_in.bias], dt, lambda: f32(self.conv_in.bias))
         if x_nchw.shape[1] > CIN_PAD:
             raise NotImplementedError("conv_in with more than 64 input channels")
-        return ops.conv3x3(ops.to_nhwc(x_nchw, dt, CIN_PAD), w, b, hilo=ops.PRECISE_RESIDUAL)
+        if res is None:
+            return ops.conv3x3(ops.to_nhwc(x_nchw, dt, CIN_PAD), w, b, hilo=ops.PRECISE_RESIDUAL)
+        return ops.conv3x3(ops.to_nhwc(x_nchw, dt, CIN_PAD), w, b, res=res, hilo=ops.PRECISE_RESIDUAL)
 
     def _conv_out(self, x: torch.Tensor, ctx: Ctx) -> torch.Tensor:
         dt = ctx.dtype
@@ -165,6 +169,47 @@ class _DenoiserBase(ConfigModelMixin, nn.Module):
         w = self._pk.get(name + "_w", [conv.weight], dt, lambda: pack_matrix(conv.weight, dt))
         b = self._pk.get(name + "_b", [conv.bias], dt, lambda: f32(conv.bias))
         return ops.linear(x, w, b, res=res, out_scale=scale, hilo=ops.PRECISE_RESIDUAL and res is not None)
+
+    # The trunk AttributeEncoderModel and ControlNetModel share: conv_in + down + mid of a UNet and 12+1 zero 1x1 convs.
+    def _build_encoder_trunk(self, in_channels, boc, down_block_types, layers_per_block, tlayers, heads, cross_attention_dim,
+                             norm_eps, act_fn, norm_num_groups, downsample_padding, mid_block_scale_factor):
+        n = len(down_block_types)
+        temb_c = boc[0] * 4
+        self.conv_in = Conv2d(in_channels, boc[0], 3, padding=1)
+        self.time_embedding = TimestepEmbedding(boc[0], temb_c)
+        self.down_blocks = nn.ModuleList()
+        self.controlnet_down_blocks = nn.ModuleList()
+        out_c = boc[0]
+        self.controlnet_down_blocks.append(zero_module(Conv2d(out_c, out_c, 1)))
+        for i, kind in enumerate(down_block_types):
+            in_c, out_c = out_c, boc[i]
+            self.down_blocks.append(get_down_block(
+                kind, num_layers=layers_per_block, transformer_layers_per_block=tlayers[i], in_channels=in_c,
+                out_channels=out_c, temb_channels=temb_c, add_downsample=i != n - 1, resnet_eps=norm_eps,
+                resnet_act_fn=act_fn, resnet_groups=norm_num_groups, cross_attention_dim=cross_attention_dim,
+                num_attention_heads=heads[i], downsample_padding=downsample_padding))
+            for _ in range(layers_per_block):
+                self.controlnet_down_blocks.append(zero_module(Conv2d(out_c, out_c, 1)))
+            if i != n - 1:
+                self.controlnet_down_blocks.append(zero_module(Conv2d(out_c, out_c, 1)))
+        self.controlnet_mid_block = zero_module(Conv2d(boc[-1], boc[-1], 1))
+        self.mid_block = UNetMidBlock2DCrossAttn(
+            boc[-1], temb_c, resnet_eps=norm_eps, resnet_groups=norm_num_groups, num_attention_heads=heads[-1],
+            cross_attention_dim=cross_attention_dim, output_scale_factor=mid_block_scale_factor,
+            transformer_layers_per_block=tlayers[-1])
+
+    def _run_encoder_trunk(self, x, ctx: Ctx, scales):
+        """x = the conv_in output -> (12 zero-conv outputs, the mid one, raw skips, raw mid), all NHWC; ``scales``: the 12 + 1
+        host floats that ride as the zero convs' ``out_scale`` (mid block last)."""
+        skips = (x,)
+        for blk in self.down_blocks:
+            x, st = blk(x, ctx)
+            skips += st
+        x = self.mid_block(x, ctx)
+        res = [self._zero_conv(f"z{i}", z, t, ctx, scale=scales[i])
+               for i, (t, z) in enumerate(zip(skips, self.controlnet_down_blocks))]
+        mid = self._zero_conv("zmid", self.controlnet_mid_block, x, ctx, scale=scales[-1])
+        return res, mid, skips, x
 
 
 def _exchange_channels(block_out_channels, layers_per_block):
@@ -458,31 +503,9 @@ class AttributeEncoderModel(_DenoiserBase):
             raise NotImplementedError("configuration outside the SD-1.x family the MI355X hot path implements")
         heads = _as_tuple(num_attention_heads, n)
         tlayers = list(_as_tuple(transformer_layers_per_block, n))
-        boc = tuple(block_out_channels)
-        temb_c = boc[0] * 4
-
-        self.conv_in = Conv2d(in_channels, boc[0], 3, padding=1)
-        self.time_embedding = TimestepEmbedding(boc[0], temb_c)
-        self.down_blocks = nn.ModuleList()
-        self.controlnet_down_blocks = nn.ModuleList()
-        out_c = boc[0]
-        self.controlnet_down_blocks.append(zero_module(Conv2d(out_c, out_c, 1)))
-        for i, kind in enumerate(down_block_types):
-            in_c, out_c = out_c, boc[i]
-            self.down_blocks.append(get_down_block(
-                kind, num_layers=layers_per_block, transformer_layers_per_block=tlayers[i], in_channels=in_c,
-                out_channels=out_c, temb_channels=temb_c, add_downsample=i != n - 1, resnet_eps=norm_eps,
-                resnet_act_fn=act_fn, resnet_groups=norm_num_groups, cross_attention_dim=cross_attention_dim,
-                num_attention_heads=heads[i], downsample_padding=downsample_padding))
-            for _ in range(layers_per_block):
-                self.controlnet_down_blocks.append(zero_module(Conv2d(out_c, out_c, 1)))
-            if i != n - 1:
-                self.controlnet_down_blocks.append(zero_module(Conv2d(out_c, out_c, 1)))
-        self.controlnet_mid_block = zero_module(Conv2d(boc[-1], boc[-1], 1))
-        self.mid_block = UNetMidBlock2DCrossAttn(
-            boc[-1], temb_c, resnet_eps=norm_eps, resnet_groups=norm_num_groups, num_attention_heads=heads[-1],
-            cross_attention_dim=cross_attention_dim, output_scale_factor=mid_block_scale_factor,
-            transformer_layers_per_block=tlayers[-1])
+        self._build_encoder_trunk(in_channels, tuple(block_out_channels), down_block_types, layers_per_block, tlayers, heads,
+                                  cross_attention_dim, norm_eps, act_fn, norm_num_groups, downsample_padding,
+                                  mid_block_scale_factor)
         self._finish_init()
 
     @classmethod
@@ -537,16 +560,7 @@ class AttributeEncoderModel(_DenoiserBase):
             return [v(t) for t in res], v(mid), tuple(v(t) for t in raw_down), v(raw_mid)
         ctx = self._begin(B, timestep, controlnet_cond.device, encoder_hidden_states)
         x = self._conv_in(controlnet_cond, ctx)  # `sample` is ignored, as in the reference
-        skips = (x,)
-        for blk in self.down_blocks:
-            x, st = blk(x, ctx)
-            skips += st
-        raw_down = skips
-        x = self.mid_block(x, ctx)
-        raw_mid = x
-        s = float(conditioning_scale)
-        res = [self._zero_conv(f"z{i}", z, t, ctx, scale=s) for i, (t, z) in enumerate(zip(skips, self.controlnet_down_blocks))]
-        mid = self._zero_conv("zmid", self.controlnet_mid_block, x, ctx, scale=s)
+        res, mid, raw_down, raw_mid = self._run_encoder_trunk(x, ctx, [float(conditioning_scale)] * (len(self.controlnet_down_blocks) + 1))
         v = ops.as_nchw_view
         return [v(t) for t in res], v(mid), tuple(v(t) for t in raw_down), v(raw_mid)
 
@@ -723,3 +737,157 @@ class AttributeDecoderModel(_DenoiserBase):
         if not return_dict:
             return out
         return UNet2DConditionOutput(sample=out)
+
+
+# =====================================================================================================
+@dataclass
+class ControlNetOutput:
+    down_block_res_samples: Tuple[torch.Tensor] = None
+    mid_block_res_sample: torch.Tensor = None
+
+
+CONTROLNET_AUTOGRAD_MSG = (
+    "ControlNetModel is inference only on the MI355X path: it was called with autograd recording and parameters or inputs "
+    "that require gradients.  Wrap the call in torch.no_grad() or call .requires_grad_(False).")
+
+
+class ControlNetModel(_DenoiserBase):
+    """Control of the UNet by an image (ref 2530-3266): the trunk of ``AttributeEncoderModel`` fed by
+    ``conv_in(sample) + controlnet_cond_embedding(controlnet_cond)``.  ``forward(..., return_dict=False)`` returns
+    ``(down_block_res_samples list[12], mid_block_res_sample)`` (ref 3260-3261), which go into
+    ``UNet2DConditionModel.forward`` as ``down_block_additional_residuals`` / ``mid_block_additional_residual``."""
+
+    @register_to_config
+    def __init__(
+        self,
+        in_channels: int = 4,
+        conditioning_channels: int = 3,
+        flip_sin_to_cos: bool = True,
+        freq_shift: int = 0,
+        down_block_types: Tuple[str, ...] = ("CrossAttnDownBlock2D", "CrossAttnDownBlock2D", "CrossAttnDownBlock2D", "DownBlock2D"),
+        only_cross_attention: Union[bool, Tuple[bool]] = False,
+        block_out_channels: Tuple[int, ...] = (320, 640, 1280, 1280),
+        layers_per_block: int = 2,
+        downsample_padding: int = 1,
+        mid_block_scale_factor: float = 1,
+        act_fn: str = "silu",
+        norm_num_groups: Optional[int] = 32,
+        norm_eps: float = 1e-5,
+        cross_attention_dim: int = 1280,
+        transformer_layers_per_block: Union[int, Tuple[int, ...]] = 1,
+        encoder_hid_dim: Optional[int] = None,
+        encoder_hid_dim_type: Optional[str] = None,
+        attention_head_dim: Union[int, Tuple[int, ...]] = 8,
+        num_attention_heads: Optional[Union[int, Tuple[int, ...]]] = None,
+        use_linear_projection: bool = False,
+        class_embed_type: Optional[str] = None,
+        addition_embed_type: Optional[str] = None,
+        addition_time_embed_dim: Optional[int] = None,
+        num_class_embeds: Optional[int] = None,
+        upcast_attention: bool = False,
+        resnet_time_scale_shift: str = "default",
+        projection_class_embeddings_input_dim: Optional[int] = None,
+        controlnet_conditioning_channel_order: str = "rgb",
+        conditioning_embedding_out_channels: Optional[Tuple[int, ...]] = (16, 32, 96, 256),
+        global_pool_conditions: bool = False,
+        addition_embed_type_num_heads: int = 64,
+    ):
+        super().__init__()
+        num_attention_heads = num_attention_heads or attention_head_dim
+        n = len(down_block_types)
+        if len(block_out_channels) != n:
+            raise ValueError("block_out_channels and down_block_types must have the same length")
+        if controlnet_conditioning_channel_order not in ("rgb", "bgr"):
+            raise ValueError(f"unknown `controlnet_conditioning_channel_order`: {controlnet_conditioning_channel_order}")
+        _reject_inactive(encoder_hid_dim=encoder_hid_dim, encoder_hid_dim_type=encoder_hid_dim_type,
+                         class_embed_type=class_embed_type, addition_embed_type=addition_embed_type,
+                         num_class_embeds=num_class_embeds)
+        if (use_linear_projection or upcast_attention or resnet_time_scale_shift != "default"
+                or global_pool_conditions or norm_num_groups is None
+                or only_cross_attention not in (False, (False,) * n, [False] * n)):
+            raise NotImplementedError("configuration outside the SD-1.x family the MI355X hot path implements")
+        emb_c = tuple(conditioning_embedding_out_channels)
+        if emb_c[-1] % 64:
+            raise NotImplementedError("conditioning_embedding_out_channels[-1] must be a multiple of 64: the embedding's "
+                                      "conv_out runs on the implicit GEMM, which adds it to conv_in(sample)")
+        heads = _as_tuple(num_attention_heads, n)
+        tlayers = list(_as_tuple(transformer_layers_per_block, n))
+        boc = tuple(block_out_channels)
+        self._build_encoder_trunk(in_channels, boc, down_block_types, layers_per_block, tlayers, heads, cross_attention_dim,
+                                  norm_eps, act_fn, norm_num_groups, downsample_padding, mid_block_scale_factor)
+        self.controlnet_cond_embedding = ControlNetConditioningEmbedding(
+            conditioning_embedding_channels=boc[0], conditioning_channels=conditioning_channels, block_out_channels=emb_c)
+        self._finish_init()
+
+    @classmethod
+    def from_unet(cls, unet: UNet2DConditionModel, controlnet_conditioning_channel_order: str = "rgb",
+                  conditioning_embedding_out_channels: Optional[Tuple[int, ...]] = (16, 32, 96, 256),
+                  load_weights_from_unet: bool = True):
+        c = unet.config
+        m = cls(
+            encoder_hid_dim=c.get("encoder_hid_dim"), encoder_hid_dim_type=c.get("encoder_hid_dim_type"),
+            addition_embed_type=c.get("addition_embed_type"), addition_time_embed_dim=c.get("addition_time_embed_dim"),
+            transformer_layers_per_block=c.get("transformer_layers_per_block", 1), in_channels=c["in_channels"],
+            flip_sin_to_cos=c["flip_sin_to_cos"], freq_shift=c["freq_shift"], down_block_types=c["down_block_types"],
+            only_cross_attention=c["only_cross_attention"], block_out_channels=c["block_out_channels"],
+            layers_per_block=c["layers_per_block"], downsample_padding=c["downsample_padding"],
+            mid_block_scale_factor=c["mid_block_scale_factor"], act_fn=c["act_fn"],
+            norm_num_groups=c["norm_num_groups"], norm_eps=c["norm_eps"], cross_attention_dim=c["cross_attention_dim"],
+            attention_head_dim=c["attention_head_dim"], num_attention_heads=c["num_attention_heads"],
+            use_linear_projection=c["use_linear_projection"], class_embed_type=c["class_embed_type"],
+            num_class_embeds=c["num_class_embeds"], upcast_attention=c["upcast_attention"],
+            resnet_time_scale_shift=c["resnet_time_scale_shift"],
+            projection_class_embeddings_input_dim=c["projection_class_embeddings_input_dim"],
+            controlnet_conditioning_channel_order=controlnet_conditioning_channel_order,
+            conditioning_embedding_out_channels=conditioning_embedding_out_channels)
+        if load_weights_from_unet:  # ref 2904-2913
+            m.conv_in.load_state_dict(unet.conv_in.state_dict())
+            m.time_embedding.load_state_dict(unet.time_embedding.state_dict())
+            m.down_blocks.load_state_dict(unet.down_blocks.state_dict())
+            m.mid_block.load_state_dict(unet.mid_block.state_dict())
+        return m
+
+    def forward(
+        self,
+        sample: torch.Tensor,
+        timestep: Union[torch.Tensor, float, int],
+        encoder_hidden_states: torch.Tensor,
+        controlnet_cond: torch.Tensor,
+        conditioning_scale: float = 1.0,
+        class_labels: Optional[torch.Tensor] = None,
+        timestep_cond: Optional[torch.Tensor] = None,
+        attention_mask: Optional[torch.Tensor] = None,
+        added_cond_kwargs: Optional[Dict[str, torch.Tensor]] = None,
+        cross_attention_kwargs: Optional[Dict[str, Any]] = None,
+        guess_mode: bool = False,
+        return_dict: bool = True,
+    ):
+        _reject_inactive(class_labels=class_labels, timestep_cond=timestep_cond, attention_mask=attention_mask,
+                         added_cond_kwargs=added_cond_kwargs, cross_attention_kwargs=cross_attention_kwargs)
+        if self._autograd_mode(sample, controlnet_cond, encoder_hidden_states):
+            raise NotImplementedError(CONTROLNET_AUTOGRAD_MSG)
+        B, _, H, W = sample.shape
+        ctx = self._begin(B, timestep, sample.device, encoder_hidden_states)
+        dt = ctx.dtype
+        # ref 3123-3132: a `bgr` image is flipped to rgb -- here the first layer's weights are, at pack time
+        bgr = self.config["controlnet_conditioning_channel_order"] == "bgr"
+        emb = self.controlnet_cond_embedding
+        h = emb(controlnet_cond, dt, bgr=bgr)
+        if tuple(h.shape[:3]) != (B, H, W):
+            raise ValueError(f"controlnet_cond {tuple(controlnet_cond.shape)} embeds to a {tuple(h.shape[1:3])} map for a "
+                             f"{(H, W)} sample")
+        w = self._pk.get("ce_w", [emb.conv_out.weight], dt, lambda: pack_conv3x3(emb.conv_out.weight, dt))
+        b = self._pk.get("ce_b", [emb.conv_out.bias], dt, lambda: f32(emb.conv_out.bias))
+        # ref 3201-3204: sample = conv_in(sample) + embedding; the add is conv_in's residual operand (no launch, one rounding)
+        x = self._conv_in(sample, ctx, res=ops.conv3x3(h, w, b))
+        s, n = float(conditioning_scale), len(self.controlnet_down_blocks) + 1
+        if guess_mode and not self.config["global_pool_conditions"]:  # ref 3245-3249: torch.logspace(-1, 0, 13) * scale, as host floats
+            scales = [10.0 ** (-1.0 + i / (n - 1)) * s for i in range(n)]
+        else:
+            scales = [s] * n
+        res, mid, _, _ = self._run_encoder_trunk(x, ctx, scales)
+        v = ops.as_nchw_view
+        res, mid = [v(t) for t in res], v(mid)
+        if not return_dict:
+            return res, mid
+        return ControlNetOutput(down_block_res_samples=res, mid_block_res_sample=mid)

@@ -376,3 +376,61 @@ def zero_module(m: nn.Module) -> nn.Module:
     for p in m.parameters():
         nn.init.zeros_(p)
     return m
+
+
+# ---------------------------------------------------------------------------------------------------
+def pack_cond_conv3x3(weight: torch.Tensor, dtype, stride: int = 1, image: bool = False, bgr: bool = False) -> torch.Tensor:
+    """[Co, Ci, 3, 3] -> the weight image ``ops.cond_conv3x3`` reads (include/ur_kernels.h, ur_cond_conv3x3):
+    [Co / 16][Cp / CC][STEPS][64 lanes][8] with CC = ``ops.cond_conv_kchunk(Ci, stride, image)``, Cp = Ci rounded up to
+    CC, STEPS = ceil(9 * CC / 32); element j of lane l of step s holds k = 32 s + 8 (l // 16) + j = tap * CC + c of output
+    channel 16 nb + l % 16, zero where tap >= 9 or the channel is padding.  ``bgr``: the input-channel axis is flipped
+    here, so the kernel reads a BGR image as it lies in memory."""
+    co, ci = weight.shape[:2]
+    cc = ops.cond_conv_kchunk(ci, stride, image)
+    cp = _ceil(ci, cc)
+    steps = _ceil(9 * cc, 32) // 32
+    if co % 16:
+        raise ValueError("pack_cond_conv3x3: output channels are a multiple of 16")
+    w = weight.detach()
+    if bgr:
+        w = w.flip(1)
+    w = torch.nn.functional.pad(w.permute(0, 2, 3, 1).reshape(co, 9, ci), (0, cp - ci))  # [Co, tap, Cp]
+    w = w.reshape(co, 9, cp // cc, cc).permute(0, 2, 1, 3).reshape(co, cp // cc, 9 * cc)  # k = tap * CC + c per chunk
+    w = torch.nn.functional.pad(w, (0, steps * 32 - 9 * cc))
+    w = w.reshape(co // 16, 16, cp // cc, steps, 4, 8).permute(0, 2, 3, 4, 1, 5)            # lane = 16 * (k // 8 % 4) + n
+    return w.to(dtype).contiguous()
+
+
+class ControlNetConditioningEmbedding(nn.Module):
+    """diffusers' ``ControlNetConditioningEmbedding`` (reference models/controlnet.py, ``controlnet_cond_embedding``):
+    conv_in, then per level a stride-1 and a stride-2 3x3 conv, SiLU after each, and a zero-initialised conv_out; parameter
+    names ``conv_in``, ``blocks.0 ...``, ``conv_out`` as there.  ``forward`` takes the caller's NCHW image and runs the
+    seven narrow convs as seven ``ops.cond_conv3x3`` launches; it returns the ``block_out_channels[-1]``-channel NHWC map,
+    and the model that owns the embedding runs ``conv_out`` (whose result it needs as a residual operand)."""
+
+    def __init__(self, conditioning_embedding_channels: int, conditioning_channels: int = 3,
+                 block_out_channels=(16, 32, 96, 256)):
+        super().__init__()
+        boc = tuple(block_out_channels)
+        if not 1 <= conditioning_channels <= 4 or any(c % 16 or c > 256 for c in boc):
+            raise NotImplementedError("conditioning embedding: 1-4 image channels and widths that are multiples of 16 up to 256")
+        self.conv_in = Conv2d(conditioning_channels, boc[0], 3, padding=1)
+        self.blocks = nn.ModuleList()
+        for i in range(len(boc) - 1):
+            self.blocks.append(Conv2d(boc[i], boc[i], 3, padding=1))
+            self.blocks.append(Conv2d(boc[i], boc[i + 1], 3, padding=1, stride=2))
+        self.conv_out = zero_module(Conv2d(boc[-1], conditioning_embedding_channels, 3, padding=1))
+        self._pk = PackCache()
+
+    def forward(self, cond_nchw: torch.Tensor, dtype, bgr: bool = False) -> torch.Tensor:
+        if cond_nchw.dtype not in ops.DT_ANY or not cond_nchw.is_contiguous():
+            cond_nchw = cond_nchw.float().contiguous()  # boundary plumbing for exotic inputs
+        convs = [self.conv_in] + list(self.blocks)
+        x = cond_nchw
+        for i, conv in enumerate(convs):
+            s, img = conv.stride[0], i == 0
+            w = self._pk.get(f"w{i}", [conv.weight], (dtype, bgr),
+                             lambda: pack_cond_conv3x3(conv.weight, dtype, s, image=img, bgr=bgr and img))
+            b = self._pk.get(f"b{i}", [conv.bias], dtype, lambda: f32(conv.bias))
+            x = ops.cond_conv3x3(x, w, b, n_out=conv.out_channels, stride=s, act=ops.ACT_SILU, dtype=dtype, image=img)
+        return x

@@ -542,6 +542,56 @@ def conv3x3(x, w, bias=None, *, x1=None, stride=1, ups=False, rowadd=None, res=N
     return out
 
 
+def cond_conv_kchunk(cin: int, stride: int = 1, image: bool = False) -> int:
+    """The k chunk (8, 16 or 32 input channels) in which ``ur_cond_conv3x3`` walks this layer: what its packed weight
+    image is laid out by (``layers.pack_cond_conv3x3``).  Host only; raises for a layer the kernel refuses."""
+    cc = _lib.load().ur_cond_conv3x3_kchunk(int(cin), int(stride), int(image))
+    check(min(cc, 0), "ur_cond_conv3x3_kchunk")
+    return cc
+
+
+def cond_conv_weight_numel(cin: int, n_out: int, stride: int = 1, image: bool = False) -> int:
+    cc = cond_conv_kchunk(cin, stride, image)
+    return (n_out // 16) * (-(-cin // cc)) * (-(-9 * cc // 32)) * 512
+
+
+def cond_conv3x3(x, w, bias, *, n_out, stride=1, act=ACT_NONE, dtype=None, image=False, out=None):
+    """Direct 3x3 conv, pad 1, stride 1 | 2, for narrow maps (``ur_cond_conv3x3``): NHWC ``x`` [B, H, W, Cin] with Cin and
+    ``n_out`` multiples of 16 up to 256 -> [B, Ho, Wo, n_out], fp32 ``bias``, optional SiLU, one rounding.  ``image``: ``x``
+    is instead the caller's contiguous NCHW tensor [B, 1..4, H, W] in fp16 / bf16 / fp32, rounded to ``dtype`` on the way
+    in.  ``w``: the image of ``layers.pack_cond_conv3x3`` for the same (stride, image).  ``out``: where the result goes
+    (default: a new tensor)."""
+    _require_gpu(x)
+    lib = _lib.load()
+    if x.dim() != 4 or not x.is_contiguous():
+        raise ValueError("cond_conv3x3: x is a contiguous 4-d tensor (NHWC, or NCHW with image=True)")
+    if image:
+        B, Cin, H, W = x.shape
+        dtype = dtype if dtype is not None else (x.dtype if x.dtype in DT else None)
+        if x.dtype not in DT_ANY or dtype not in DT:
+            raise ValueError("cond_conv3x3: an fp16 / bf16 / fp32 image and an fp16 / bf16 compute dtype")
+    else:
+        B, H, W, Cin = x.shape
+        if dtype not in (None, x.dtype) or x.dtype not in DT:
+            raise ValueError("cond_conv3x3: an NHWC input is already in the compute dtype (fp16 / bf16)")
+        dtype = x.dtype
+    if w.dtype != dtype or not w.is_contiguous() or w.numel() != cond_conv_weight_numel(Cin, n_out, stride, image):
+        raise ValueError("cond_conv3x3: w is the layers.pack_cond_conv3x3 image of this layer in the compute dtype")
+    if bias.dtype != torch.float32 or bias.numel() != n_out or not bias.is_contiguous():
+        raise ValueError("cond_conv3x3: bias is fp32 [n_out]")
+    Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
+    if out is None:
+        out = torch.empty(B, Ho, Wo, n_out, dtype=dtype, device=x.device)
+    elif tuple(out.shape) != (B, Ho, Wo, n_out) or out.dtype != dtype or not out.is_contiguous():
+        raise ValueError("cond_conv3x3: out is a contiguous [B, Ho, Wo, n_out] tensor in the compute dtype")
+    e0 = _prof_begin()
+    check(lib.ur_cond_conv3x3(x.data_ptr(), DT_ANY[x.dtype], int(image), w.data_ptr(), bias.data_ptr(), out.data_ptr(), B, H, W,
+                              Cin, n_out, int(stride), int(act), DT[dtype], _stream()), "ur_cond_conv3x3")
+    _prof_end(e0, "cond_conv3x3", 2.0 * out.numel() * 9 * Cin,
+              float(x.numel() * x.element_size() + (out.numel() + w.numel()) * out.element_size()))
+    return out
+
+
 # conv -> GroupNorm (+ SiLU) with the normalisation as the split-K second pass (ur_igemm_splitk_gn).  OFF by default: parity is
 # green (tests/test_ops_gpu.py), but the step is 0.07 ms SLOWER with it (85.42 / 85.65 -> 85.01 / 84.92 steps/s alternating
 # on one box, profiles/r04_splitk_gn_ab.txt).  Round 4 blamed the 160-byte runs in which one workgroup per (sample, group) reads
