@@ -416,6 +416,27 @@ typedef struct ur_add_item {
 int ur_add_hilo_multi(const ur_add_item* items, int n, int dtype, void* stream);
 int ur_sizeof_add_item(void);
 
+/* LoRA merge over a list of weight matrices in ONE launch (an addition to ABI 17; csrc/lora.hip).  Per item
+ *     w[n][k] = cast_dtype( base[n][k] + scale * sum_{r = 0 .. R-1} rscale[r] * up[n][r] * down[r][k] )
+ * items: a HOST table of nine int64_t words per item, [n][9] = { base, w, up, down, rscale, N, K, R, scale }: five device
+ * addresses, three counts, and the IEEE bits of the fp32 `scale` in the low half of the last word (the header's struct and
+ * constant census is pinned by tests/test_host_cpu.py, so the items are a word table like ur_adamw8_multi's, and the two
+ * limits are host calls: at most ur_lora_multi_max() items per launch, R at most ur_lora_max_rank(), which is >= 256).
+ * base, w: DISTINCT [N][K] row-major matrices in `dtype` (UR_DT_F16, UR_DT_BF16 or UR_DT_F32, one per launch), element
+ * aligned; a conv weight [Co][Ci][kh][kw] is the matrix [Co][Ci * kh * kw] (what diffusers' _fuse_lora multiplies).
+ * up: fp32 [N][R], down: fp32 [R][K], rscale: fp32 [R] or 0 for ones.  Several adapters at once are the concatenation
+ * of their factors along r, rscale[r] = alpha / rank times the adapter's weight: the kernel knows no "adapter".
+ * fp32 arithmetic: p = rscale[r] * up[n][r] (rounded; skipped without rscale), acc = fma(p, down[r][k], acc) for r ascending
+ * from acc = 0, then one fma(scale, acc, base) and one rounding to dtype.  Deterministic, no atomics.
+ * R == 0 is valid (up / down may then be 0): w receives the bits of base, no arithmetic -- how unfuse / unload restore.
+ * Any N, K >= 1 (below 2^31); rows whose byte length is no multiple of the 4-element access take an element-wise path.
+ * Before any launch: a null base / w (or up / down with R > 0), N <= 0, K <= 0, R < 0, w == base, a misaligned address or
+ * an unknown dtype: UR_E_BADARG; R over the rank limit or more workgroups than one grid holds: UR_E_UNSUPPORTED. */
+int ur_lora_merge_multi(const int64_t* items, int n, int dtype, void* stream);
+int ur_lora_multi_max(void);
+int ur_lora_max_rank(void);
+int ur_lora_item_words(void);
+
 /* Sinusoidal timestep embedding of nt (1 or B) fp32 timesteps: out[b][:] = [cos | sin] (flip) or
  * [sin | cos]; fp32 math. */
 int ur_timestep_embedding(const float* t, int nt, int B, int dim, int flip_sin_to_cos, float freq_shift,

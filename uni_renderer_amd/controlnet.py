@@ -12,7 +12,9 @@ caller are zero-copy NCHW *views* (channels-last strides) of those NHWC buffers,
 back without a copy -- the 13+13 exchange tensors never change layout between the three networks.
 
 Configuration branches that the SD-1.x checkpoint family leaves inactive (class / addition embeddings,
-encoder_hid_proj, GLIGEN, LoRA scale, attention masks) raise ``NotImplementedError``.
+encoder_hid_proj, GLIGEN, attention masks) raise ``NotImplementedError``, and so does every key of
+``cross_attention_kwargs`` other than ``scale``.  ``cross_attention_kwargs={"scale": s}`` is the LoRA scale: the UNet merges
+its adapters at ``s`` before the call (``lora.py``); the other three networks have no adapters and ignore it.
 """
 from __future__ import annotations
 
@@ -25,6 +27,7 @@ import torch
 import torch.nn as nn
 
 from . import ops
+from .lora import UNetLoraMixin, scale_of
 from .layers import Attention, ControlNetConditioningEmbedding, Conv2d, Ctx, GroupNorm, PackCache, ResnetBlock2D, \
     TimestepEmbedding, f32, pack_conv3x3, pack_matrix, zero_module
 from .modeling_utils import ConfigModelMixin, register_to_config
@@ -222,7 +225,7 @@ def _exchange_channels(block_out_channels, layers_per_block):
 
 
 # =====================================================================================================
-class UNet2DConditionModel(_DenoiserBase):
+class UNet2DConditionModel(UNetLoraMixin, _DenoiserBase):
     """Image stream.  ``forward(..., return_dict=False)`` returns
     ``(sample, raw_down_block_res_samples[12], raw_mid_block_sample, up_block_res_samples[13])`` (ref 1163-1164)."""
 
@@ -374,10 +377,18 @@ class UNet2DConditionModel(_DenoiserBase):
         return_dict: bool = True,
     ):
         _reject_inactive(class_labels=class_labels, timestep_cond=timestep_cond, attention_mask=attention_mask,
-                         cross_attention_kwargs=cross_attention_kwargs, added_cond_kwargs=added_cond_kwargs,
+                         added_cond_kwargs=added_cond_kwargs,
                          down_intrablock_additional_residuals=down_intrablock_additional_residuals,
                          encoder_attention_mask=encoder_attention_mask)
-        if self._autograd_mode(sample, encoder_hidden_states, down_block_additional_residuals, mid_block_additional_residual):
+        lora_scale = scale_of(cross_attention_kwargs)
+        autograd = self._autograd_mode(sample, encoder_hidden_states, down_block_additional_residuals, mid_block_additional_residual)
+        if self._lora is not None:
+            if autograd:
+                from .train_step import LORA_AUTOGRAD_MSG
+
+                raise NotImplementedError(LORA_AUTOGRAD_MSG)
+            self._lora_apply(lora_scale)  # re-merges only when the wanted scale differs from the merged one
+        if autograd:
             return self._forward_autograd(sample, timestep, encoder_hidden_states, down_block_additional_residuals,
                                           mid_block_additional_residual, return_dict)
         state = self.forward_down_mid(sample, timestep, encoder_hidden_states)
@@ -547,7 +558,8 @@ class AttributeEncoderModel(_DenoiserBase):
         return_dict: bool = True,
     ):
         _reject_inactive(class_labels=class_labels, timestep_cond=timestep_cond, attention_mask=attention_mask,
-                         added_cond_kwargs=added_cond_kwargs, cross_attention_kwargs=cross_attention_kwargs)
+                         added_cond_kwargs=added_cond_kwargs)
+        scale_of(cross_attention_kwargs)  # a LoRA scale is accepted and ignored: this network has no adapters
         B = controlnet_cond.shape[0]
         if self._autograd_mode(controlnet_cond, encoder_hidden_states):
             from . import train_step as TS
@@ -692,7 +704,8 @@ class AttributeDecoderModel(_DenoiserBase):
         return_dict: bool = True,
     ):
         _reject_inactive(class_labels=class_labels, timestep_cond=timestep_cond, attention_mask=attention_mask,
-                         added_cond_kwargs=added_cond_kwargs, cross_attention_kwargs=cross_attention_kwargs)
+                         added_cond_kwargs=added_cond_kwargs)
+        scale_of(cross_attention_kwargs)  # a LoRA scale is accepted and ignored: this network has no adapters
         if mid_block_additional_residual is None:
             raise ValueError("mid_block_additional_residual is mandatory (the reference crashes on None, ref 2476)")
         B = sample.shape[0]
@@ -863,7 +876,8 @@ class ControlNetModel(_DenoiserBase):
         return_dict: bool = True,
     ):
         _reject_inactive(class_labels=class_labels, timestep_cond=timestep_cond, attention_mask=attention_mask,
-                         added_cond_kwargs=added_cond_kwargs, cross_attention_kwargs=cross_attention_kwargs)
+                         added_cond_kwargs=added_cond_kwargs)
+        scale_of(cross_attention_kwargs)  # a LoRA scale is accepted and ignored: this network has no adapters
         if self._autograd_mode(sample, controlnet_cond, encoder_hidden_states):
             raise NotImplementedError(CONTROLNET_AUTOGRAD_MSG)
         B, _, H, W = sample.shape

@@ -33,9 +33,14 @@ def dual_stream_step(unet, enc, dec, x_t, cond, ehs, t_img, t_attr, run_decoder:
     if side is None:
         res, mid, raw_enc, raw_mid_enc = enc(x_t, t_attr, encoder_hidden_states=ehs, controlnet_cond=cond,
                                              conditioning_scale=conditioning_scale, return_dict=False)
+        # a step executor runs the weights as they are merged, like the grouped and hoisted executors, which never pass
+        # through ``forward``: the caller sets the LoRA scale (``UniRendererPipeline`` does, once per sampling call, before it
+        # takes the weights signature), and handing the merged scale back keeps ``forward`` from re-merging at its default
+        merged = getattr(unet, "lora_scale", None)
         img_pred, raw_unet, raw_mid_unet, _ = unet(
             x_t, t_img, encoder_hidden_states=ehs, down_block_additional_residuals=res,
-            mid_block_additional_residual=mid, return_dict=False)
+            mid_block_additional_residual=mid, return_dict=False,
+            cross_attention_kwargs=None if merged is None else {"scale": merged})
         out = {"img_pred": img_pred}
         if run_decoder:
             out["attr_pred"] = dec(sample=raw_mid_enc, down_block_res_samples=raw_enc, timestep=t_attr,

@@ -25,6 +25,7 @@ import torch
 
 from .controlnet import AttributeDecoderModel, AttributeEncoderModel, UNet2DConditionModel
 from . import ops
+from .lora import read_lora_file, scale_of
 from .graph import GraphedDualStreamStep, GraphedHoistedStep, dual_stream_step
 from .schedulers import DDIMScheduler, retrieve_timesteps
 from .unet_2d_blocks import freeu_state
@@ -101,6 +102,27 @@ class UniRendererPipeline:
     def disable_freeu(self):
         """ref 762-764."""
         self.unet.disable_freeu()
+
+    # ---- LoRA (the reference's LoraLoaderMixin, UNet part) ----------------------------------------------
+    def load_lora_weights(self, pretrained_model_name_or_path_or_dict, weight_name=None, adapter_name: str = "default", **kwargs):
+        """Loads a LoRA file (a state dict, a ``.safetensors`` file or a directory holding ``weight_name``; local files only)
+        into the UNet.  ``unet.``-prefixed and unprefixed keys go to ``unet.load_attn_procs``; ``.alpha`` entries are the
+        network alphas.  The text encoder is not part of this package: ``text_encoder.`` keys raise ``NotImplementedError``."""
+        sd = read_lora_file(pretrained_model_name_or_path_or_dict, weight_name)
+        te = [k for k in sd if k.startswith(("text_encoder.", "text_encoder_2."))]
+        if te:
+            raise NotImplementedError(f"LoRA key {te[0]!r}: adapters for the text encoder are not supported (the text "
+                                      "encoder is not run by this package)")
+        self.unet.load_attn_procs(sd, adapter_name=adapter_name)
+
+    def unload_lora_weights(self):
+        self.unet.unload_lora()
+
+    def fuse_lora(self, lora_scale: float = 1.0, **kwargs):
+        self.unet.fuse_lora(lora_scale)
+
+    def unfuse_lora(self, **kwargs):
+        self.unet.unfuse_lora()
 
     def _weights_signature(self):
         """(device, (data_ptr, version) of every parameter) of the three networks: in-place updates bump ``_version``,
@@ -409,6 +431,7 @@ class UniRendererPipeline:
         ``image_latents`` / ``mask_latents`` (already VAE-encoded, scaled) bypass the VAE; ``output_type="latent"``
         returns the six latents instead of decoded images."""
         self._guidance_scale = guidance_scale
+        self.unet._lora_apply(scale_of(cross_attention_kwargs))  # before any _weights_signature(): graphs see merged weights
         device = self._execution_device
         batch_size = 1 if isinstance(prompt, str) else (len(prompt) if prompt is not None else prompt_embeds.shape[0])
         prompt_embeds, negative_prompt_embeds = self.encode_prompt(
@@ -515,6 +538,7 @@ class UniRendererPipeline:
         """Rendering: attributes -> image (enc + unet per step; the decoder is not run, ref 1631-1639).
         ``attr_latents`` ([B,28,h,w], mask first) bypasses the VAE encodes of the seven attribute images."""
         self._guidance_scale = guidance_scale
+        self.unet._lora_apply(scale_of(cross_attention_kwargs))  # before any _weights_signature(): graphs see merged weights
         device = self._execution_device
         batch_size = 1 if isinstance(prompt, str) else (len(prompt) if prompt is not None else prompt_embeds.shape[0])
         prompt_embeds, negative_prompt_embeds = self.encode_prompt(

@@ -244,6 +244,9 @@ def _down_mid(net, x, temb_act, ehs, dt):
 FREEU_AUTOGRAD_MSG = ("FreeU is enabled on this network's up blocks, but the differentiable path has no backward for it: FreeU is a "
                       "sampling-time switch -- call disable_freeu() for training, or run the forward under torch.no_grad()")
 
+LORA_AUTOGRAD_MSG = ("a LoRA adapter is loaded on this network, but the differentiable path does not train adapters (they are merged "
+                     "into the weights): call unload_lora() for training, or run the forward under torch.no_grad()")
+
 
 def _up_out(net, x, skips: List[torch.Tensor], temb_act, ehs, dt, extras=None, collect=None):
     """Up path + conv_out.  ``extras``: per-resnet tensors added after each resnet(/transformer) of an ``UpRes*`` block
@@ -315,6 +318,8 @@ def encoder_forward(enc, cond_nhwc, ehs, t_attr, dt, conditioning_scale: float =
 def unet_forward(unet, x_nhwc, ehs, t_img, dt, res=None, mid_res=None, collect_up: bool = False):
     """UNet2DConditionModel (controlnet.py:781-1166).  ``x_nhwc`` [B,H,W,CIN_PAD]; ``res`` / ``mid_res``: the encoder's
     residuals (NHWC) or None.  Returns (img_pred, raw_down[12], raw_mid, up_res[13] | None), NHWC."""
+    if getattr(unet, "_lora", None) is not None:
+        raise NotImplementedError(LORA_AUTOGRAD_MSG)
     B, dev = x_nhwc.shape[0], x_nhwc.device
     with _batched_casts(unet, dt):
         tu = _time(unet, t_img, B, dt, dev)
