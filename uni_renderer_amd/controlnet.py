@@ -28,12 +28,14 @@ import torch.nn as nn
 
 from . import ops
 from .lora import UNetLoraMixin, scale_of
+from . import packs as R
 from .layers import Attention, ControlNetConditioningEmbedding, Conv2d, Ctx, GroupNorm, PackCache, ResnetBlock2D, \
-    TimestepEmbedding, f32, pack_conv3x3, pack_matrix, zero_module
+    TimestepEmbedding, zero_module
 from .modeling_utils import ConfigModelMixin, register_to_config
 from .unet_2d_blocks import FREEU_KEYS, UNetMidBlock2DCrossAttn, freeu_enabled, get_down_block, get_up_block
 
 CIN_PAD = 64  # conv_in reads its 4 / 28 input channels zero-padded to one 64-channel K chunk
+_CONV_IN = R.conv3x3_padded(CIN_PAD)
 
 
 @dataclass
@@ -88,10 +90,8 @@ class _DenoiserBase(ConfigModelMixin, nn.Module):
         ctx = Ctx(dt, B)
         ctx.ehs = self._tokens(encoder_hidden_states, dt)
         if self._cross:  # every cross-attention K and V^T of the network in two GEMMs (they only see the prompt)
-            wks = [a.to_k.weight for a in self._cross]
-            wvs = [a.to_v.weight for a in self._cross]
-            wk = self._pk.get("xk", wks, dt, lambda: torch.cat([pack_matrix(w, dt) for w in wks], 0).contiguous())
-            wv = self._pk.get("xv", wvs, dt, lambda: torch.cat([pack_matrix(w, dt) for w in wvs], 0).contiguous())
+            wk = R.one(self._pk, R.matrix_rows, [a.to_k for a in self._cross], dt)
+            wv = R.one(self._pk, R.matrix_rows, [a.to_v for a in self._cross], dt)
             ctx.kc = ops.linear(ctx.ehs, wk)
             ctx.vtc = ops.vt_proj(ctx.ehs, wv)
         t = timestep
@@ -105,10 +105,7 @@ class _DenoiserBase(ConfigModelMixin, nn.Module):
         boc0 = self.config["block_out_channels"][0]
         t_emb = ops.timestep_embedding(t, B, boc0, self.config["flip_sin_to_cos"], self.config["freq_shift"], dt)
         semb = self.time_embedding(t_emb, silu_out=True)  # SiLU(emb), the only form the resnets consume
-        ws = [r.time_emb_proj.weight for r in self._resnets]
-        bs = [r.time_emb_proj.bias for r in self._resnets]
-        wcat = self._pk.get("temb_w", ws, dt, lambda: torch.cat([pack_matrix(w, dt) for w in ws], 0).contiguous())
-        bcat = self._pk.get("temb_b", bs, dt, lambda: torch.cat([f32(b) for b in bs], 0).contiguous())
+        wcat, bcat = R.one(self._pk, R.linear_rows, [r.time_emb_proj for r in self._resnets], dt)
         ctx.temb = ops.linear(semb, wcat, bcat)  # [B, sum Cout]
         return ctx
 
@@ -150,8 +147,7 @@ class _DenoiserBase(ConfigModelMixin, nn.Module):
     def _conv_in(self, x_nchw: torch.Tensor, ctx: Ctx, res=None) -> torch.Tensor:
         """``res``: an NHWC tensor added in the conv's epilogue (one launch, one rounding)."""
         dt = ctx.dtype
-        w = self._pk.get("cin_w", [self.conv_in.weight], dt, lambda: pack_conv3x3(self.conv_in.weight, dt, CIN_PAD))
-        b = self._pk.get("cin_b", [self.conv_in.bias], dt, lambda: f32(self.conv_in.bias))
+        w, b = R.one(self._pk, _CONV_IN, self.conv_in, dt)
         if x_nchw.shape[1] > CIN_PAD:
             raise NotImplementedError("conv_in with more than 64 input channels")
         if res is None:
@@ -160,17 +156,14 @@ class _DenoiserBase(ConfigModelMixin, nn.Module):
 
     def _conv_out(self, x: torch.Tensor, ctx: Ctx) -> torch.Tensor:
         dt = ctx.dtype
-        g, b = self._pk.get("no", [self.conv_norm_out.weight, self.conv_norm_out.bias], dt,
-                            lambda: (f32(self.conv_norm_out.weight), f32(self.conv_norm_out.bias)))
-        w = self._pk.get("co_w", [self.conv_out.weight], dt, lambda: pack_conv3x3(self.conv_out.weight, dt))
-        cb = self._pk.get("co_b", [self.conv_out.bias], dt, lambda: f32(self.conv_out.bias))
+        g, b = R.one(self._pk, R.affine, self.conv_norm_out, dt)
+        w, cb = R.one(self._pk, R.conv3x3_tap, self.conv_out, dt)
         h = ops.groupnorm(x, g, b, self.conv_norm_out.eps, groups=self.conv_norm_out.num_groups, silu=True)
         return ops.conv3x3(h, w, cb, n_out=self.conv_out.weight.shape[0])
 
-    def _zero_conv(self, name: str, conv: Conv2d, x: torch.Tensor, ctx: Ctx, res=None, scale: float = 1.0):
+    def _zero_conv(self, conv: Conv2d, x: torch.Tensor, ctx: Ctx, res=None, scale: float = 1.0):
         dt = ctx.dtype
-        w = self._pk.get(name + "_w", [conv.weight], dt, lambda: pack_matrix(conv.weight, dt))
-        b = self._pk.get(name + "_b", [conv.bias], dt, lambda: f32(conv.bias))
+        w, b = R.one(self._pk, R.linear, conv, dt)
         return ops.linear(x, w, b, res=res, out_scale=scale, hilo=ops.PRECISE_RESIDUAL and res is not None)
 
     # The trunk AttributeEncoderModel and ControlNetModel share: conv_in + down + mid of a UNet and 12+1 zero 1x1 convs.
@@ -209,9 +202,9 @@ class _DenoiserBase(ConfigModelMixin, nn.Module):
             x, st = blk(x, ctx)
             skips += st
         x = self.mid_block(x, ctx)
-        res = [self._zero_conv(f"z{i}", z, t, ctx, scale=scales[i])
+        res = [self._zero_conv(z, t, ctx, scale=scales[i])
                for i, (t, z) in enumerate(zip(skips, self.controlnet_down_blocks))]
-        mid = self._zero_conv("zmid", self.controlnet_mid_block, x, ctx, scale=scales[-1])
+        mid = self._zero_conv(self.controlnet_mid_block, x, ctx, scale=scales[-1])
         return res, mid, skips, x
 
 
@@ -729,9 +722,9 @@ class AttributeDecoderModel(_DenoiserBase):
         skips = tuple(ops.to_nhwc(s, dt) for s in down_block_res_samples)
         if down_block_additional_residuals is not None:  # ref 2446-2461
             skips = tuple(
-                self._zero_conv(f"c{i}", z, ops.to_nhwc(e, dt), ctx, res=s)
-                for i, (s, e, z) in enumerate(zip(skips, down_block_additional_residuals, self.control_down_blocks)))
-        x = self._zero_conv("cmid", self.control_mid_block, ops.to_nhwc(mid_block_additional_residual, dt), ctx,
+                self._zero_conv(z, ops.to_nhwc(e, dt), ctx, res=s)
+                for s, e, z in zip(skips, down_block_additional_residuals, self.control_down_blocks))
+        x = self._zero_conv(self.control_mid_block, ops.to_nhwc(mid_block_additional_residual, dt), ctx,
                             res=ops.to_nhwc(sample, dt))  # ref 2476-2477
         ups = None
         if up_block_additional_residuals is not None:  # only consumed by UpRes* block types
@@ -890,8 +883,7 @@ class ControlNetModel(_DenoiserBase):
         if tuple(h.shape[:3]) != (B, H, W):
             raise ValueError(f"controlnet_cond {tuple(controlnet_cond.shape)} embeds to a {tuple(h.shape[1:3])} map for a "
                              f"{(H, W)} sample")
-        w = self._pk.get("ce_w", [emb.conv_out.weight], dt, lambda: pack_conv3x3(emb.conv_out.weight, dt))
-        b = self._pk.get("ce_b", [emb.conv_out.bias], dt, lambda: f32(emb.conv_out.bias))
+        w, b = R.one(self._pk, R.conv3x3_tap, emb.conv_out, dt)
         # ref 3201-3204: sample = conv_in(sample) + embedding; the add is conv_in's residual operand (no launch, one rounding)
         x = self._conv_in(sample, ctx, res=ops.conv3x3(h, w, b))
         s, n = float(conditioning_scale), len(self.controlnet_down_blocks) + 1

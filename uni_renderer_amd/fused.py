@@ -28,9 +28,10 @@ import torch
 
 from . import _experiments as X
 from . import ops, tchain
-from .controlnet import CIN_PAD, _compute_dtype
-from .layers import (LOG2E, Attention, BasicTransformerBlock, ResnetBlock2D, Transformer2DModel, f32, geglu_perm,
-                     pack_conv3x3, pack_matrix)
+from .controlnet import _CONV_IN, CIN_PAD, _compute_dtype
+from . import packs as R
+from .layers import LOG2E, Attention, BasicTransformerBlock, ResnetBlock2D, Transformer2DModel
+from .packs import PackCache, stacked
 from .unet_2d_blocks import freeu_params
 
 
@@ -47,28 +48,6 @@ TCHAIN_MIN_ROWS = X.number("tchain_min_rows", 16384)
 HEAD_MAJOR_QK = X.flag("head_major_qk", True)
 
 
-class _Packs:
-    """Cache of stream-stacked packed tensors keyed by (name, module ids, dtype) + parameter versions."""
-
-    def __init__(self):
-        self._store = {}
-
-    def get(self, name, mods, params, dtype, build):
-        key = (name, tuple(id(m) for m in mods), dtype)
-        ver = tuple((p.data_ptr(), p._version) for p in params)
-        hit = self._store.get(key)
-        if hit is not None and hit[0] == ver:
-            return hit[1]
-        with torch.no_grad():
-            val = build()
-        self._store[key] = (ver, val)
-        return val
-
-
-def _stk(ts):
-    return torch.stack(list(ts), 0).contiguous()
-
-
 class GroupedDualStreamStep:
     """enc + unet + dec step with every op of the two diffusion streams issued as one grouped kernel."""
 
@@ -78,7 +57,7 @@ class GroupedDualStreamStep:
         residual path, which is 55 % of the step's fp16 error variance, for 2 extra bytes per
         element on those tensors.  Default: env UR_PRECISE_RESIDUAL (1 / 0), on."""
         self.unet, self.enc, self.dec = unet, enc, dec
-        self.pk = _Packs()
+        self.pk = PackCache()
         if precise_residual is None:
             precise_residual = os.environ.get("UR_PRECISE_RESIDUAL", "1") != "0"
         self.hilo = bool(precise_residual)
@@ -145,51 +124,41 @@ class GroupedDualStreamStep:
     def _resnet(self, rs: Sequence[ResnetBlock2D], x, temb, slice_, x1=None):
         S, pk, dt = len(rs), self.pk, x.dtype
         r0 = rs[0]
-        g1 = pk.get("r.g1", rs, [r.norm1.weight for r in rs], dt, lambda: _stk(f32(r.norm1.weight) for r in rs))
-        b1 = pk.get("r.b1", rs, [r.norm1.bias for r in rs], dt, lambda: _stk(f32(r.norm1.bias) for r in rs))
-        g2 = pk.get("r.g2", rs, [r.norm2.weight for r in rs], dt, lambda: _stk(f32(r.norm2.weight) for r in rs))
-        b2 = pk.get("r.b2", rs, [r.norm2.bias for r in rs], dt, lambda: _stk(f32(r.norm2.bias) for r in rs))
-        w1 = pk.get("r.w1", rs, [r.conv1.weight for r in rs], dt, lambda: _stk(pack_conv3x3(r.conv1.weight, dt, cblock=ops.conv_cblock(r.conv1.weight.shape[1])) for r in rs))
-        c1 = pk.get("r.c1", rs, [r.conv1.bias for r in rs], dt, lambda: _stk(f32(r.conv1.bias) for r in rs))
-        w2 = pk.get("r.w2", rs, [r.conv2.weight for r in rs], dt, lambda: _stk(pack_conv3x3(r.conv2.weight, dt, cblock=ops.conv_cblock(r.conv2.weight.shape[1])) for r in rs))
-        c2 = pk.get("r.c2", rs, [r.conv2.bias for r in rs], dt, lambda: _stk(f32(r.conv2.bias) for r in rs))
+        g1, b1 = stacked(pk, R.affine, [r.norm1 for r in rs], dt)
+        g2, b2 = stacked(pk, R.affine, [r.norm2 for r in rs], dt)
+        convs1, convs2 = [r.conv1 for r in rs], [r.conv2 for r in rs]
+        w1, c1 = stacked(pk, R.conv3x3, convs1, dt)
         lo, hi = slice_
         h = ops.groupnorm(x, g1, b1, r0.eps, x1=x1, groups=r0.groups, silu=True, streams=S)
         # conv1 -> norm2 -> SiLU: conv1's output has no other consumer, so where conv1 runs split-K on a small map (the
         # 16x16 / 8x8 levels) the GroupNorm is the split-K second pass and the conv output is never written (ops.conv3x3 gn=)
         h = ops.conv3x3(h, w1, c1, rowadd=temb[:, lo:hi], streams=S, cblock=ops.conv_cblock(h.shape[-1]),
-                        ws=self._ws("r.w1ws", rs, [r.conv1.weight for r in rs], w1, h, streams=S),
+                        ws=self._ws("r.w1ws", R.conv3x3, convs1, w1, h, streams=S),
                         gn=(g2, b2, r0.eps, r0.groups, True))
         if r0.conv_shortcut is not None and ops.FOLD_SHORTCUT:
             # the 1x1 conv_shortcut over (x | x1) rides in conv2's K loop (ur_igemm_desc.t0 / t1): one launch less and no
             # round trip of its output through memory
-            w2s = pk.get("r.w2s", rs, [t for r in rs for t in (r.conv2.weight, r.conv_shortcut.weight)], dt,
-                         lambda: _stk(torch.cat([pack_conv3x3(r.conv2.weight, dt, cblock=ops.conv_cblock(r.conv2.weight.shape[1])),
-                                                 pack_matrix(r.conv_shortcut.weight, dt)], 1) for r in rs))
-            c2s = pk.get("r.c2s", rs, [t for r in rs for t in (r.conv2.bias, r.conv_shortcut.bias)], dt,
-                         lambda: _stk(f32(r.conv2.bias) + f32(r.conv_shortcut.bias) for r in rs))
+            w2s, c2s = stacked(pk, R.fold, rs, dt)
             return ops.conv3x3(h, w2s, c2s, tail=(x, x1), out_scale=1.0 / r0.output_scale_factor, streams=S, hilo=self.hilo,
                                cblock=ops.conv_cblock(h.shape[-1]),
-                               ws=self._ws("r.w2sws", rs, [t for r in rs for t in (r.conv2.weight, r.conv_shortcut.weight)], w2s, h,
-                                           tail=(x, x1), streams=S))
+                               ws=self._ws("r.w2sws", R.fold, rs, w2s, h, tail=(x, x1), streams=S))
         if r0.conv_shortcut is not None:
-            ws = pk.get("r.ws", rs, [r.conv_shortcut.weight for r in rs], dt,
-                        lambda: _stk(pack_matrix(r.conv_shortcut.weight, dt) for r in rs))
-            bs = pk.get("r.bs", rs, [r.conv_shortcut.bias for r in rs], dt, lambda: _stk(f32(r.conv_shortcut.bias) for r in rs))
+            ws, bs = stacked(pk, R.linear, [r.conv_shortcut for r in rs], dt)
             sc = ops.linear(x, ws, bs, x1=x1, streams=S)
         else:
             sc = x
+        w2, c2 = stacked(pk, R.conv3x3, convs2, dt)
         return ops.conv3x3(h, w2, c2, res=sc, out_scale=1.0 / r0.output_scale_factor, streams=S, hilo=self.hilo,
-                           cblock=ops.conv_cblock(h.shape[-1]),
-                           ws=self._ws("r.w2ws", rs, [r.conv2.weight for r in rs], w2, h, streams=S))
+                           cblock=ops.conv_cblock(h.shape[-1]), ws=self._ws("r.w2ws", R.conv3x3, convs2, w2, h, streams=S))
 
-    def _ws(self, name, mods, params, w, x, tail=None, streams=1):
+    def _ws(self, name, recipe, mods, w, x, tail=None, streams=1):
         """Stage-image copy of the packed conv weights ``w`` [S, N, K] for the weight-streaming kernel, or None where the
         LDS-tiled build is used (ops.wsconv_prefer)."""
         N, K = w.shape[-2], w.shape[-1]
         if not ops.wsconv_prefer(x, N, K, tail=tail, streams=streams):
             return None
-        return self.pk.get(name, mods, params, x.dtype, lambda: _stk(ops.wsconv_images(w[i]) for i in range(w.shape[0])))
+        return self.pk.get((name, tuple(id(m) for m in mods), x.dtype), [p for m in mods for p in recipe.params(m)],
+                           lambda: torch.stack([ops.wsconv_images(w[i]) for i in range(w.shape[0])], 0).contiguous())
 
     def _attn(self, as_: Sequence[Attention], xn, residual, kc, vtc, kv_slice):
         S, pk, dt = len(as_), self.pk, xn.dtype
@@ -197,22 +166,18 @@ class GroupedDualStreamStep:
         Bt, T, _ = xn.shape
         H, d, C = a0.heads, a0.dim_head, a0.inner
         cs = d ** -0.5 * LOG2E
-        wo = pk.get("a.wo", as_, [a.to_out[0].weight for a in as_], dt, lambda: _stk(pack_matrix(a.to_out[0].weight, dt) for a in as_))
-        bo = pk.get("a.bo", as_, [a.to_out[0].bias for a in as_], dt, lambda: _stk(f32(a.to_out[0].bias) for a in as_))
+        wo, bo = stacked(pk, R.linear, [a.to_out[0] for a in as_], dt)
         if not a0.is_cross:
             if QKV_ONE_LAUNCH and T % 64 == 0:
                 # q | k | v as ONE grouped GEMM: the value columns leave the epilogue transposed (ur_igemm_desc.out_vt), which
                 # retires the separate V^T projection launch of every self-attention of the 32x32 .. 8x8 levels
-                wqkv = pk.get("a.wqkv", as_, [p for a in as_ for p in (a.to_q.weight, a.to_k.weight, a.to_v.weight)], dt,
-                              lambda: _stk(torch.cat([pack_matrix(a.to_q.weight, dt), pack_matrix(a.to_k.weight, dt),
-                                                      pack_matrix(a.to_v.weight, dt)], 0) for a in as_))
+                wqkv = stacked(pk, R.matrix_rows, [(a.to_q, a.to_k, a.to_v) for a in as_], dt)
                 ops.set_site("qkv")
                 qk, vt = ops.linear(xn, wqkv, streams=S, out_scale=math.sqrt(cs), vt_cols=C, vt_tokens=T)
                 ops.set_site(None)
             else:
-                wqk = pk.get("a.wqk", as_, [p for a in as_ for p in (a.to_q.weight, a.to_k.weight)], dt,
-                             lambda: _stk(torch.cat([pack_matrix(a.to_q.weight, dt), pack_matrix(a.to_k.weight, dt)], 0) for a in as_))
-                wv = pk.get("a.wv", as_, [a.to_v.weight for a in as_], dt, lambda: _stk(pack_matrix(a.to_v.weight, dt) for a in as_))
+                wqk = stacked(pk, R.matrix_rows, [(a.to_q, a.to_k) for a in as_], dt)
+                wv = stacked(pk, R.matrix, [a.to_v for a in as_], dt)
                 vt_first = X.flag("vt_first", True)
                 ops.set_site("qk")
                 if not vt_first:
@@ -226,7 +191,7 @@ class GroupedDualStreamStep:
                 f.join(vt)
             o = ops.attention(qk, qk, vt, B=Bt, H=H, Tq=T, Tk=T, d=d, ldq=2 * C, ldk=2 * C, q_off=0, k_off=C, scale=0.0)
         else:
-            wq = pk.get("a.wq", as_, [a.to_q.weight for a in as_], dt, lambda: _stk(pack_matrix(a.to_q.weight, dt) for a in as_))
+            wq = stacked(pk, R.matrix, [a.to_q for a in as_], dt)
             ops.set_site("q")
             q = ops.linear(xn, wq, streams=S, out_scale=cs)
             lo, hi = kv_slice
@@ -240,28 +205,14 @@ class GroupedDualStreamStep:
     def _tblock(self, bs: Sequence[BasicTransformerBlock], x, kc, vtc, kv_slice):
         S, pk, dt = len(bs), self.pk, x.dtype
 
-        def ln(name, get):
-            g = pk.get(name + ".g", bs, [get(b).weight for b in bs], dt, lambda: _stk(f32(get(b).weight) for b in bs))
-            b_ = pk.get(name + ".b", bs, [get(b).bias for b in bs], dt, lambda: _stk(f32(get(b).bias) for b in bs))
-            return g, b_
-
-        g, b_ = ln("t.n1", lambda b: b.norm1)
+        g, b_ = stacked(pk, R.affine, [b.norm1 for b in bs], dt)
         x = self._attn([b.attn1 for b in bs], ops.layernorm(x, g, b_, bs[0].norm1.eps, streams=S), x, None, None, None)
-        g, b_ = ln("t.n2", lambda b: b.norm2)
+        g, b_ = stacked(pk, R.affine, [b.norm2 for b in bs], dt)
         x = self._attn([b.attn2 for b in bs], ops.layernorm(x, g, b_, bs[0].norm2.eps, streams=S), x, kc, vtc, kv_slice)
-        g, b_ = ln("t.n3", lambda b: b.norm3)
+        g, b_ = stacked(pk, R.affine, [b.norm3 for b in bs], dt)
         xn = ops.layernorm(x, g, b_, bs[0].norm3.eps, streams=S)
-        projs = [b.ff.net[0].proj for b in bs]
-        outs = [b.ff.net[2] for b in bs]
-        nh = projs[0].weight.shape[0] // 2
-
-        def build_in():
-            perm = geglu_perm(nh, projs[0].weight.device)
-            return (_stk(pack_matrix(p.weight, dt)[perm] for p in projs), _stk(f32(p.bias)[perm] for p in projs))
-
-        w_in, b_in = pk.get("t.ffi", bs, [p for pr in projs for p in (pr.weight, pr.bias)], dt, build_in)
-        w_out = pk.get("t.ffo", bs, [o.weight for o in outs], dt, lambda: _stk(pack_matrix(o.weight, dt) for o in outs))
-        b_out = pk.get("t.ffb", bs, [o.bias for o in outs], dt, lambda: _stk(f32(o.bias) for o in outs))
+        w_in, b_in = stacked(pk, R.geglu, [b.ff.net[0].proj for b in bs], dt)
+        w_out, b_out = stacked(pk, R.linear, [b.ff.net[2] for b in bs], dt)
         ops.set_site("ffi")
         gg = ops.linear(xn, w_in, b_in, act=ops.ACT_GEGLU, streams=S)
         ops.set_site("ffo")
@@ -278,19 +229,10 @@ class GroupedDualStreamStep:
         with one difference on the weight side: the chain folds the q / k scale sqrt(d^-1/2 log2 e) into the projection WEIGHTS
         before their fp16 / bf16 cast (tchain.pack_*), where ``_attn`` applies ``out_scale`` to the fp32 accumulator."""
         S, pk, dt = len(bs), self.pk, x.dtype
-        a1, a2 = [b.attn1 for b in bs], [b.attn2 for b in bs]
-        a0 = a1[0]
+        a0 = bs[0].attn1
         Bt, T, C = x.shape
         H, d = a0.heads, a0.dim_head
-        cs = d ** -0.5 * LOG2E
-        def build_pre():
-            packs = [tchain.pack_chain_pre(t.proj_in.weight, t.proj_in.bias, b.norm1.weight, b.norm1.bias, b.attn1.to_q.weight,
-                                           b.attn1.to_k.weight, b.attn1.to_v.weight, math.sqrt(cs), dt) for b, t in zip(bs, ts)]
-            return _stk(p[0] for p in packs), _stk(p[1] for p in packs)
-
-        wsp, csp = pk.get("tc.pre", bs, [p for b, t in zip(bs, ts) for p in (
-            t.proj_in.weight, t.proj_in.bias, b.norm1.weight, b.norm1.bias, b.attn1.to_q.weight, b.attn1.to_k.weight,
-            b.attn1.to_v.weight)], dt, build_pre)
+        wsp, csp = stacked(pk, R.chain_pre, ts, dt)
         # x = the GroupNorm output: proj_in + LayerNorm1 + q / k / V^T projections in one launch
         # q / k leave the chain HEAD-MAJOR ([sample][head][token][40], round 6): a head's 64-key tile is one 5 KB run instead of 64
         # 80-byte slices of 640-byte token rows -- at the 128x128 level the slices made every XCD fetch 2.4 lines per line used and
@@ -302,40 +244,21 @@ class GroupedDualStreamStep:
         x = xr.view(Bt, T, C)
         x.lo = xr.lo.view(Bt, T, C)
 
-        def build_q():
-            packs = [tchain.pack_chain_q(b.attn1.to_out[0].weight, b.attn1.to_out[0].bias, b.norm2.weight, b.norm2.bias,
-                                         b.attn2.to_q.weight, cs, dt) for b in bs]
-            return _stk(p[0] for p in packs), _stk(p[1] for p in packs)
-
-        wsq, csq = pk.get("tc.q", bs, [p for b in bs for p in (b.attn1.to_out[0].weight, b.attn1.to_out[0].bias, b.norm2.weight,
-                                                               b.norm2.bias, b.attn2.to_q.weight)], dt, build_q)
+        wsq, csq = stacked(pk, R.chain_q, ts, dt)
         y1, q2 = tchain.chain_q(o1.view(Bt * T, C), ops.view_hilo(x, Bt * T, C), wsq, csq, bs[0].norm2.eps, streams=S,
                                 head_major_tokens=T if hm else 0)
         lo, hi = kv_slice
         o2 = ops.attention(q2.view(Bt, T, C), kc[:, :, lo:hi], vtc[:, lo:hi], B=Bt, H=H, Tq=T, Tk=kc.shape[1], d=d, ldq=C,
                            ldk=kc.stride(1), scale=0.0, q_hstride=T * d if hm else 0)
 
-        def build_ff():
-            packs = [tchain.pack_chain_ff(b.attn2.to_out[0].weight, b.attn2.to_out[0].bias, b.norm3.weight, b.norm3.bias,
-                                          b.ff.net[0].proj.weight, b.ff.net[0].proj.bias, b.ff.net[2].weight, b.ff.net[2].bias,
-                                          t.proj_out.weight, t.proj_out.bias, dt) for b, t in zip(bs, ts)]
-            return _stk(p[0] for p in packs), _stk(p[1] for p in packs)
-
-        wsf, csf = pk.get("tc.ff", bs, [p for b, t in zip(bs, ts) for p in (
-            b.attn2.to_out[0].weight, b.attn2.to_out[0].bias, b.norm3.weight, b.norm3.bias, b.ff.net[0].proj.weight,
-            b.ff.net[0].proj.bias, b.ff.net[2].weight, b.ff.net[2].bias, t.proj_out.weight, t.proj_out.bias)], dt, build_ff)
+        wsf, csf = stacked(pk, R.chain_ff, ts, dt)
         out = tchain.chain_ff(o2.view(Bt * T, C), y1, ops.view_hilo(blk_in, Bt * T, C), wsf, csf, bs[0].norm3.eps, streams=S)
         return ops.view_hilo(out, Bt, T, C)
 
     def _transformer(self, ts: Sequence[Transformer2DModel], x, kc, vtc, kv_slices):
         S, pk, dt = len(ts), self.pk, x.dtype
         Bt, H, W, Cc = x.shape
-        g = pk.get("x.g", ts, [t.norm.weight for t in ts], dt, lambda: _stk(f32(t.norm.weight) for t in ts))
-        b_ = pk.get("x.b", ts, [t.norm.bias for t in ts], dt, lambda: _stk(f32(t.norm.bias) for t in ts))
-        wi = pk.get("x.wi", ts, [t.proj_in.weight for t in ts], dt, lambda: _stk(pack_matrix(t.proj_in.weight, dt) for t in ts))
-        bi = pk.get("x.bi", ts, [t.proj_in.bias for t in ts], dt, lambda: _stk(f32(t.proj_in.bias) for t in ts))
-        wo = pk.get("x.wo", ts, [t.proj_out.weight for t in ts], dt, lambda: _stk(pack_matrix(t.proj_out.weight, dt) for t in ts))
-        bo = pk.get("x.bo", ts, [t.proj_out.bias for t in ts], dt, lambda: _stk(f32(t.proj_out.bias) for t in ts))
+        g, b_ = stacked(pk, R.affine, [t.norm for t in ts], dt)
         h = ops.groupnorm(x, g, b_, ts[0].norm.eps, groups=ts[0].groups, silu=False, streams=S)
         b0 = ts[0].transformer_blocks[0]
         # the chain kernels hard-code C = 320 (tchain.supported), 8 heads of 40, bias-free q / k / v and a feed-forward of
@@ -349,20 +272,21 @@ class GroupedDualStreamStep:
                 and all(getattr(a, nm).bias is None for a in (b0.attn1, b0.attn2) for nm in ("to_q", "to_k", "to_v"))):
             return ops.view_hilo(self._tblock_chain([t.transformer_blocks[0] for t in ts], ts, h.view(Bt, H * W, Cc),
                                                     ops.view_hilo(x, Bt, H * W, Cc), kc, vtc, kv_slices[0]), Bt, H, W, Cc)
+        wi, bi = stacked(pk, R.linear, [t.proj_in for t in ts], dt)
         ops.set_site("pi")
         h = ops.linear(h.view(Bt, H * W, Cc), wi, bi, streams=S, hilo=self.hilo)
         ops.set_site(None)
         for j in range(len(ts[0].transformer_blocks)):
             h = self._tblock([t.transformer_blocks[j] for t in ts], h, kc, vtc, kv_slices[j])
+        wo, bo = stacked(pk, R.linear, [t.proj_out for t in ts], dt)
         ops.set_site("po")
         y = ops.linear(h, wo, bo, res=ops.view_hilo(x, Bt, H * W, Cc), streams=S, hilo=self.hilo)
         ops.set_site(None)
         return ops.view_hilo(y, Bt, H, W, Cc)
 
-    def _conv(self, name, convs, x, stride=1, ups=False):
+    def _conv(self, convs, x, stride=1, ups=False):
         S, pk, dt = len(convs), self.pk, x.dtype
-        w = pk.get(name + ".w", convs, [c.weight for c in convs], dt, lambda: _stk(pack_conv3x3(c.weight, dt, cblock=ops.conv_cblock(c.weight.shape[1])) for c in convs))
-        b = pk.get(name + ".b", convs, [c.bias for c in convs], dt, lambda: _stk(f32(c.bias) for c in convs))
+        w, b = stacked(pk, R.conv3x3, convs, dt)
         return ops.conv3x3(x, w, b, stride=stride, ups=ups, streams=S, hilo=self.hilo, cblock=ops.conv_cblock(x.shape[-1]))
 
     # ------------------------------------------------------------------ per-phase context (temb, prompt K / V^T)
@@ -378,22 +302,15 @@ class GroupedDualStreamStep:
             tslices[id(r)] = (off, off + r.out_channels)
             off += r.out_channels
         if temb:
-            key = tuple(id(r) for rl in resnet_lists for r in rl)
-            wt = pk.get(("p.wt", key), nets, [r.time_emb_proj.weight for rl in resnet_lists for r in rl], dt,
-                        lambda: _stk(torch.cat([pack_matrix(r.time_emb_proj.weight, dt) for r in rl], 0) for rl in resnet_lists))
-            bt = pk.get(("p.bt", key), nets, [r.time_emb_proj.bias for rl in resnet_lists for r in rl], dt,
-                        lambda: _stk(torch.cat([f32(r.time_emb_proj.bias) for r in rl], 0) for rl in resnet_lists))
+            wt, bt = stacked(pk, R.linear_rows, [[r.time_emb_proj for r in rl] for rl in resnet_lists], dt)
             temb = ops.linear(semb, wt, bt, streams=S)  # [S*B, sum Cout]
         else:
             temb = None
         kc = vtc = None
         kslices = {}
         if cross_lists[0] and kv:
-            ckey = tuple(id(a) for al in cross_lists for a in al)
-            wk = pk.get(("p.wk", ckey), nets, [a.to_k.weight for al in cross_lists for a in al], dt,
-                        lambda: _stk(torch.cat([pack_matrix(a.to_k.weight, dt) for a in al], 0) for al in cross_lists))
-            wv = pk.get(("p.wv", ckey), nets, [a.to_v.weight for al in cross_lists for a in al], dt,
-                        lambda: _stk(torch.cat([pack_matrix(a.to_v.weight, dt) for a in al], 0) for al in cross_lists))
+            wk = stacked(pk, R.matrix_rows, [[a.to_k for a in al] for al in cross_lists], dt)
+            wv = stacked(pk, R.matrix_rows, [[a.to_v for a in al] for al in cross_lists], dt)
             B, Tk, Cc = ehs.shape
             n = wk.shape[1]
             kc = torch.empty(S * B, Tk, n, dtype=dt, device=ehs.device)
@@ -402,8 +319,7 @@ class GroupedDualStreamStep:
                 # columns leave the epilogue transposed (ur_igemm_desc.out_vt) into a zero-filled [S*B, n, Tpad] tensor
                 # (77 keys: the pad columns must be zero for the attention kernel) -- instead of a K GEMM plus one
                 # transposed V projection per stream
-                wkv = pk.get(("p.wkv", ckey), nets, [t for al in cross_lists for a in al for t in (a.to_k.weight, a.to_v.weight)], dt,
-                             lambda: torch.cat([wk, wv], 1).contiguous())
+                wkv = stacked(pk, R.matrix_rows, [[a.to_k for a in al] + [a.to_v for a in al] for al in cross_lists], dt)
                 Tpad = (Tk + 63) // 64 * 64
                 vtc = torch.zeros(S * B, n, Tpad, dtype=dt, device=ehs.device)
                 ops.igemm(x0=ehs, w=wkv, out=kc, M=B * Tk, N=2 * n, K=Cc, c0=Cc, ldx0=Cc, ldw=Cc, ldc=n, n_store=n, zbatch=S, zx=0,
@@ -437,40 +353,26 @@ class GroupedDualStreamStep:
         c = self.unet.config
         ts = torch.cat(list(tvals)).contiguous() if S > 1 else tvals[0].contiguous()
         t_emb = ops.timestep_embedding(ts, S * B, c["block_out_channels"][0], c["flip_sin_to_cos"], c["freq_shift"], dt)
-        tes = [n.time_embedding for n in nets]
-        w1 = pk.get("te.w1", tes, [t.linear_1.weight for t in tes], dt, lambda: _stk(pack_matrix(t.linear_1.weight, dt) for t in tes))
-        b1 = pk.get("te.b1", tes, [t.linear_1.bias for t in tes], dt, lambda: _stk(f32(t.linear_1.bias) for t in tes))
-        w2 = pk.get("te.w2", tes, [t.linear_2.weight for t in tes], dt, lambda: _stk(pack_matrix(t.linear_2.weight, dt) for t in tes))
-        b2 = pk.get("te.b2", tes, [t.linear_2.bias for t in tes], dt, lambda: _stk(f32(t.linear_2.bias) for t in tes))
+        w1, b1 = stacked(pk, R.linear, [n.time_embedding.linear_1 for n in nets], dt)
+        w2, b2 = stacked(pk, R.linear, [n.time_embedding.linear_2 for n in nets], dt)
         return ops.linear(ops.linear(t_emb, w1, b1, act=ops.ACT_SILU, streams=S), w2, b2, act=ops.ACT_SILU, streams=S)
 
-    def _exchange(self, name, z_enc, z_dec, t, B, scale, dt):
+    def _exchange(self, z_enc, z_dec, t, B, scale, dt):
         """t = [enc ; unet] stacked.  Returns [unet + zc(enc)*scale ; enc + cd(unet)] (z_dec given) or only the first half."""
-        pk = self.pk
-        half = t.numel() // 2
-        Cc = t.shape[-1]
+        pk, half, Cc = self.pk, t.numel() // 2, t.shape[-1]
         if z_dec is not None:
-            mods = [z_enc, z_dec]
-            w = pk.get((name, "w", scale), mods, [m.weight for m in mods], dt,
-                       lambda: _stk([pack_matrix(z_enc.weight, dt) * scale if scale != 1.0 else pack_matrix(z_enc.weight, dt),
-                                     pack_matrix(z_dec.weight, dt)]))
-            b = pk.get((name, "b", scale), mods, [m.bias for m in mods], dt,
-                       lambda: _stk([f32(z_enc.bias) * scale, f32(z_dec.bias)]))
+            w, b = stacked(pk, [R.scaled_linear(scale), R.linear], [z_enc, z_dec], dt)
             tt = t.view(2, -1, Cc)
             tl = ops.lo_of(t)
             y = ops.linear(tt, w, b, res=tt[1], res_zstride=-half, streams=2, hilo=self.hilo,
                            res_lo=(tl.view(2, -1, Cc)[1] if tl is not None else None))
             return ops.view_hilo(y, *t.shape)
-        w = pk.get((name, "w1", scale), [z_enc], [z_enc.weight], dt, lambda: (pack_matrix(z_enc.weight, dt) * scale).contiguous())
-        b = pk.get((name, "b1", scale), [z_enc], [z_enc.bias], dt, lambda: f32(z_enc.bias) * scale)
+        w, b = R.one(pk, R.scaled_linear(scale), z_enc, dt)
         tl = ops.lo_of(t)
         return ops.linear(t[:B], w, b, res=t[B:], hilo=self.hilo, res_lo=(tl[B:] if tl is not None else None))
 
     def _conv_in(self, nets, x_in):
-        pk, dt = self.pk, x_in.dtype
-        cins = [n.conv_in for n in nets]
-        wci = pk.get("cin.w", cins, [m.weight for m in cins], dt, lambda: _stk(pack_conv3x3(m.weight, dt, CIN_PAD) for m in cins))
-        bci = pk.get("cin.b", cins, [m.bias for m in cins], dt, lambda: _stk(f32(m.bias) for m in cins))
+        wci, bci = stacked(self.pk, _CONV_IN, [n.conv_in for n in nets], x_in.dtype)
         return ops.conv3x3(x_in, wci, bci, streams=len(nets), hilo=self.hilo)
 
     def _down_mid(self, nets, x, ctx, on_skip):
@@ -487,7 +389,7 @@ class GroupedDualStreamStep:
                     x = self._transformer(tsf, x, kc, vtc, self._kvs(tsf[0], ksl))
                 on_skip(x)
             if blks[0].downsamplers is not None:
-                x = self._conv("ds", [b.downsamplers[0].conv for b in blks], x, stride=2)
+                x = self._conv([b.downsamplers[0].conv for b in blks], x, stride=2)
                 on_skip(x)
         mids = [n.mid_block for n in nets]
         x = self._resnet([m.resnets[0] for m in mids], x, temb, tsl[id(mids[0].resnets[0])])
@@ -520,26 +422,20 @@ class GroupedDualStreamStep:
                 ucs = [b.upsamplers[0].conv for b in blks]
                 tgt = tuple(up_skips[-1].shape[1:3])  # the reference's upsample_size (controlnet.py:1129-1130)
                 if tgt == (2 * x.shape[1], 2 * x.shape[2]):
-                    x = self._conv("us", ucs, x, ups=True)
+                    x = self._conv(ucs, x, ups=True)
                 else:  # latent side not a multiple of 8: general nearest resize, then the conv
-                    x = self._conv("us", ucs, ops.resize_nearest(x, tgt))
+                    x = self._conv(ucs, ops.resize_nearest(x, tgt))
         return x
 
     def _head(self, nets, x):
         """conv_norm_out -> SiLU -> conv_out of ``nets`` (output channels padded to the widest): [S*B, H, W, n_out]."""
         pk, dt, S = self.pk, x.dtype, len(nets)
         norms = [n.conv_norm_out for n in nets]
-        g = pk.get("out.g", norms, [m.weight for m in norms], dt, lambda: _stk(f32(m.weight) for m in norms))
-        b_ = pk.get("out.b", norms, [m.bias for m in norms], dt, lambda: _stk(f32(m.bias) for m in norms))
+        g, b_ = stacked(pk, R.affine, norms, dt)
         h = ops.groupnorm(x, g, b_, norms[0].eps, groups=norms[0].num_groups, silu=True, streams=S)
         couts = [n.conv_out for n in nets]
         n_out = max(m.weight.shape[0] for m in couts)  # 4 (image) / 28 (attributes): pad to the widest
-
-        def pad_rows(t, n):
-            return t if t.shape[0] == n else torch.cat([t, t.new_zeros((n - t.shape[0],) + tuple(t.shape[1:]))], 0)
-
-        wco = pk.get("out.w", couts, [m.weight for m in couts], dt, lambda: _stk(pad_rows(pack_conv3x3(m.weight, dt), n_out) for m in couts))
-        bco = pk.get("out.cb", couts, [m.bias for m in couts], dt, lambda: _stk(pad_rows(f32(m.bias), n_out) for m in couts))
+        wco, bco = stacked(pk, R.conv_out(n_out), couts, dt)
         return ops.conv3x3(h, wco, bco, n_out=n_out, streams=S)
 
     def _ctx_of(self, nets, parts, semb, ehs, temb=True, kv=True):
@@ -576,7 +472,7 @@ class GroupedDualStreamStep:
                 return
             i = len(up_skips)
             with self._fork(t) as f:
-                y = self._exchange(f"ex{i}", enc.controlnet_down_blocks[i], dec.control_down_blocks[i] if run_decoder else None,
+                y = self._exchange(enc.controlnet_down_blocks[i], dec.control_down_blocks[i] if run_decoder else None,
                                    t, B, scale, dt)
             up_skips.append(y)
             forks.append((f, y))
@@ -596,9 +492,9 @@ class GroupedDualStreamStep:
 
         # ================= phase 2: the mid exchange; join the sibling branch =================
         for i, t in enumerate(late):
-            up_skips.append(self._exchange(f"ex{i}", enc.controlnet_down_blocks[i],
+            up_skips.append(self._exchange(enc.controlnet_down_blocks[i],
                                            dec.control_down_blocks[i] if run_decoder else None, t, B, scale, dt))
-        x = self._exchange("exm", enc.controlnet_mid_block, dec.control_mid_block if run_decoder else None, mid, B, scale, dt)
+        x = self._exchange(enc.controlnet_mid_block, dec.control_mid_block if run_decoder else None, mid, B, scale, dt)
         for f, y in forks:
             f.join(y)
         if ctx3 is None:

@@ -39,7 +39,7 @@ import torch
 from . import ops
 from .controlnet import CIN_PAD, _compute_dtype
 from .fused import GroupedDualStreamStep
-from .layers import f32, pack_matrix
+from . import packs as R
 
 
 class _HoistedInverseOut(dict):
@@ -68,12 +68,10 @@ class HoistedSamplingStep:
         self.inv: Dict[str, object] = {}
 
     # ------------------------------------------------------------------ helpers
-    def _zero_conv(self, name, z, t, scale):
+    def _zero_conv(self, z, t, scale):
         """scale * (z(t)) as a (hi, lo) pair: one exchange 1x1 conv (controlnet.py:1752-1769 / 2446-2461) without its add."""
         g, dt = self.g, t.dtype
-        w = g.pk.get((name, "hw", scale), [z], [z.weight], dt,
-                     lambda: (pack_matrix(z.weight, dt) * scale).contiguous() if scale != 1.0 else pack_matrix(z.weight, dt))
-        b = g.pk.get((name, "hb", scale), [z], [z.bias], dt, lambda: f32(z.bias) * scale)
+        w, b = R.one(g.pk, R.scaled_linear(scale), z, dt)
         Bt, H, W, Cc = t.shape
         y = ops.linear(ops.view_hilo(t, Bt, H * W, Cc), w, b, hilo=g.hilo)
         return ops.view_hilo(y, Bt, H, W, w.shape[0])
@@ -109,13 +107,13 @@ class HoistedSamplingStep:
             # the UNet's raw skips (captured before any residual is added: controlnet.py:1075, 1112)
             raw, _ = self._run_down_mid(unet, x_fixed, CIN_PAD, tv, ehs, B, dt)
             zs = list(dec.control_down_blocks) + [dec.control_mid_block]
-            inv["fixed"] = [self._zero_conv(f"hx{i}", z, t, 1.0) for i, (z, t) in enumerate(zip(zs, raw))]
+            inv["fixed"] = [self._zero_conv(z, t, 1.0) for z, t in zip(zs, raw)]
             inv["kv1"] = self._kv_only(enc, [enc.down_blocks, enc.mid_block], ehs)
             inv["kv3"] = self._kv_only(dec, [dec.up_blocks], ehs)
         else:
             raw, _ = self._run_down_mid(enc, x_fixed, CIN_PAD, tv, ehs, B, dt)
             zs = list(enc.controlnet_down_blocks) + [enc.controlnet_mid_block]
-            inv["fixed"] = [self._zero_conv(f"hr{i}", z, t, self.scale) for i, (z, t) in enumerate(zip(zs, raw))]
+            inv["fixed"] = [self._zero_conv(z, t, self.scale) for z, t in zip(zs, raw)]
             inv["kv1"] = self._kv_only(unet, [unet.down_blocks, unet.mid_block], ehs)
             inv["kv3"] = self._kv_only(unet, [unet.up_blocks], ehs)
         return self

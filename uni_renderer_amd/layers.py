@@ -53,24 +53,6 @@ def _ceil(v: int, m: int) -> int:
 LOG2E = 1.4426950408889634
 
 
-class PackCache:
-    """Per-module cache of packed tensors keyed by (name, dtype, device, parameter versions)."""
-
-    def __init__(self):
-        self._store = {}
-
-    def get(self, name, params, dtype, build):
-        key = (name, dtype)
-        ver = tuple((p.data_ptr(), p._version, p.device) for p in params)
-        hit = self._store.get(key)
-        if hit is not None and hit[0] == ver:
-            return hit[1]
-        with torch.no_grad():
-            val = build()
-        self._store[key] = (ver, val)
-        return val
-
-
 def pack_conv3x3(weight: torch.Tensor, dtype, cin_pad: Optional[int] = None, cblock: int = 0) -> torch.Tensor:
     """[Co, Ci, 3, 3] -> [Co, 9 * Ci_pad] with k = (ky*3 + kx) * Ci_pad + c (zero padded channels), or with
     ``cblock`` > 0 in the block-outer order k = (c // cblock) * 9 * cblock + (ky*3 + kx) * cblock + c % cblock
@@ -102,6 +84,32 @@ def f32(t: torch.Tensor) -> torch.Tensor:
     return t.detach().float().contiguous()
 
 
+def pack_cond_conv3x3(weight: torch.Tensor, dtype, stride: int = 1, image: bool = False, bgr: bool = False) -> torch.Tensor:
+    """[Co, Ci, 3, 3] -> the weight image ``ops.cond_conv3x3`` reads (include/ur_kernels.h, ur_cond_conv3x3):
+    [Co / 16][Cp / CC][STEPS][64 lanes][8] with CC = ``ops.cond_conv_kchunk(Ci, stride, image)``, Cp = Ci rounded up to
+    CC, STEPS = ceil(9 * CC / 32); element j of lane l of step s holds k = 32 s + 8 (l // 16) + j = tap * CC + c of output
+    channel 16 nb + l % 16, zero where tap >= 9 or the channel is padding.  ``bgr``: the input-channel axis is flipped
+    here, so the kernel reads a BGR image as it lies in memory."""
+    co, ci = weight.shape[:2]
+    cc = ops.cond_conv_kchunk(ci, stride, image)
+    cp = _ceil(ci, cc)
+    steps = _ceil(9 * cc, 32) // 32
+    if co % 16:
+        raise ValueError("pack_cond_conv3x3: output channels are a multiple of 16")
+    w = weight.detach()
+    if bgr:
+        w = w.flip(1)
+    w = torch.nn.functional.pad(w.permute(0, 2, 3, 1).reshape(co, 9, ci), (0, cp - ci))  # [Co, tap, Cp]
+    w = w.reshape(co, 9, cp // cc, cc).permute(0, 2, 1, 3).reshape(co, cp // cc, 9 * cc)  # k = tap * CC + c per chunk
+    w = torch.nn.functional.pad(w, (0, steps * 32 - 9 * cc))
+    w = w.reshape(co // 16, 16, cp // cc, steps, 4, 8).permute(0, 2, 3, 4, 1, 5)            # lane = 16 * (k // 8 % 4) + n
+    return w.to(dtype).contiguous()
+
+
+from . import packs as R  # noqa: E402 -- the recipes build on the primitives above
+from .packs import PackCache, one  # noqa: E402,F401 -- PackCache is imported from here by its other users
+
+
 class Ctx:
     """Per-forward context handed down the module tree."""
 
@@ -130,10 +138,8 @@ class TimestepEmbedding(nn.Module):
         """Returns SiLU(emb) when ``silu_out`` (every consumer of emb in this config is a resnet's
         ``time_emb_proj(SiLU(emb))``), computed in the GEMM epilogues."""
         dt = t_emb.dtype
-        w1 = self._pk.get("w1", [self.linear_1.weight], dt, lambda: pack_matrix(self.linear_1.weight, dt))
-        b1 = self._pk.get("b1", [self.linear_1.bias], dt, lambda: f32(self.linear_1.bias))
-        w2 = self._pk.get("w2", [self.linear_2.weight], dt, lambda: pack_matrix(self.linear_2.weight, dt))
-        b2 = self._pk.get("b2", [self.linear_2.bias], dt, lambda: f32(self.linear_2.bias))
+        w1, b1 = one(self._pk, R.linear, self.linear_1, dt)
+        w2, b2 = one(self._pk, R.linear, self.linear_2, dt)
         h = ops.linear(t_emb, w1, b1, act=ops.ACT_SILU)
         return ops.linear(h, w2, b2, act=ops.ACT_SILU if silu_out else ops.ACT_NONE)
 
@@ -157,37 +163,27 @@ class ResnetBlock2D(nn.Module):
 
     def forward(self, x, ctx: Ctx, x1=None, extra_res=None):
         """x (and optional x1, concatenated on channels) NHWC -> NHWC [B,H,W,out_channels]."""
-        dt = x.dtype
-        pk = self._pk
-        g1, b1 = pk.get("n1", [self.norm1.weight, self.norm1.bias], dt, lambda: (f32(self.norm1.weight), f32(self.norm1.bias)))
-        g2, b2 = pk.get("n2", [self.norm2.weight, self.norm2.bias], dt, lambda: (f32(self.norm2.weight), f32(self.norm2.bias)))
-        w1 = pk.get("w1", [self.conv1.weight], dt,
-                    lambda: pack_conv3x3(self.conv1.weight, dt, cblock=ops.conv_cblock(self.conv1.weight.shape[1])))
-        cb1 = pk.get("cb1", [self.conv1.bias], dt, lambda: f32(self.conv1.bias))
-        w2 = pk.get("w2", [self.conv2.weight], dt,
-                    lambda: pack_conv3x3(self.conv2.weight, dt, cblock=ops.conv_cblock(self.conv2.weight.shape[1])))
-        cb2 = pk.get("cb2", [self.conv2.bias], dt, lambda: f32(self.conv2.bias))
+        dt, pk = x.dtype, self._pk
+        g1, b1 = one(pk, R.affine, self.norm1, dt)
+        g2, b2 = one(pk, R.affine, self.norm2, dt)
+        w1, cb1 = one(pk, R.conv3x3, self.conv1, dt)
         lo, hi = self.temb_slice
         h = ops.groupnorm(x, g1, b1, self.eps, x1=x1, groups=self.groups, silu=True)
         h = ops.conv3x3(h, w1, cb1, rowadd=ctx.temb[:, lo:hi], cblock=ops.conv_cblock(h.shape[-1]))
         h = ops.groupnorm(h, g2, b2, self.eps, groups=self.groups, silu=True)
         if self.conv_shortcut is not None and ops.FOLD_SHORTCUT and extra_res is None:
             # conv_shortcut rides in conv2's K loop as its 1x1 tail (ops.conv3x3 ``tail``)
-            w2s = pk.get("w2s", [self.conv2.weight, self.conv_shortcut.weight], dt,
-                         lambda: torch.cat([pack_conv3x3(self.conv2.weight, dt, cblock=ops.conv_cblock(self.conv2.weight.shape[1])),
-                                            pack_matrix(self.conv_shortcut.weight, dt)], 1).contiguous())
-            cb2s = pk.get("cb2s", [self.conv2.bias, self.conv_shortcut.bias], dt,
-                          lambda: f32(self.conv2.bias) + f32(self.conv_shortcut.bias))
+            w2s, cb2s = one(pk, R.fold, self, dt)
             return ops.conv3x3(h, w2s, cb2s, tail=(x, x1), out_scale=1.0 / self.output_scale_factor, hilo=ops.PRECISE_RESIDUAL,
                                cblock=ops.conv_cblock(h.shape[-1]))
         if self.conv_shortcut is not None:
-            ws = pk.get("ws", [self.conv_shortcut.weight], dt, lambda: pack_matrix(self.conv_shortcut.weight, dt))
-            bs = pk.get("bs", [self.conv_shortcut.bias], dt, lambda: f32(self.conv_shortcut.bias))
+            ws, bs = one(pk, R.linear, self.conv_shortcut, dt)
             sc = ops.linear(x, ws, bs, x1=x1)
         else:
             if x1 is not None:
                 raise RuntimeError("concat input requires a conv_shortcut (in_channels != out_channels)")
             sc = x
+        w2, cb2 = one(pk, R.conv3x3, self.conv2, dt)
         return ops.conv3x3(h, w2, cb2, res=sc, out_scale=1.0 / self.output_scale_factor, hilo=ops.PRECISE_RESIDUAL,
                            cblock=ops.conv_cblock(h.shape[-1]))
 
@@ -210,34 +206,31 @@ class Attention(nn.Module):
 
     def forward(self, xn, ctx: Ctx, residual):
         """xn: normalised tokens [B,T,C]; returns residual + to_out(attention)."""
-        dt = xn.dtype
-        pk = self._pk
+        dt, pk = xn.dtype, self._pk
         B, T, _ = xn.shape
         H, d, C = self.heads, self.dim_head, self.inner
         # The softmax scale and the change to base 2 are folded into the q (and, when q|k come from one GEMM, k)
         # projection epilogues in fp32 -- before the single rounding to fp16/bf16 -- so the attention kernel sees
         # scores in log2 units (ur_attention scale = 0) and spends no multiply-add per score.
         cs = d ** -0.5 * LOG2E
-        wo = pk.get("wo", [self.to_out[0].weight], dt, lambda: pack_matrix(self.to_out[0].weight, dt))
-        bo = pk.get("bo", [self.to_out[0].bias], dt, lambda: f32(self.to_out[0].bias))
+        wo, bo = one(pk, R.linear, self.to_out[0], dt)
         if self.is_cross and ctx.kc is not None and self.kv_slice is not None:
             # K / V^T of the prompt were projected once for the whole network (controlnet._begin)
             lo, hi = self.kv_slice
-            wq = pk.get("wq", [self.to_q.weight], dt, lambda: pack_matrix(self.to_q.weight, dt))
+            wq = one(pk, R.matrix, self.to_q, dt)
             q = ops.linear(xn, wq, out_scale=cs)
             o = ops.attention(q, ctx.kc[:, :, lo:hi], ctx.vtc[:, lo:hi], B=B, H=H, Tq=T, Tk=ctx.kc.shape[1], d=d,
                               ldq=C, ldk=ctx.kc.stride(1), scale=0.0)
             return ops.linear(o, wo, bo, res=residual, hilo=ops.PRECISE_RESIDUAL)
-        wv = pk.get("wv", [self.to_v.weight], dt, lambda: pack_matrix(self.to_v.weight, dt))
+        wv = one(pk, R.matrix, self.to_v, dt)
         if not self.is_cross:
-            wqk = pk.get("wqk", [self.to_q.weight, self.to_k.weight], dt,
-                         lambda: torch.cat([pack_matrix(self.to_q.weight, dt), pack_matrix(self.to_k.weight, dt)], 0))
+            wqk = one(pk, R.matrix_rows, (self.to_q, self.to_k), dt)
             qk = ops.linear(xn, wqk, out_scale=math.sqrt(cs))  # [B,T,2C] = q | k, each carrying sqrt(cs)
             vt = ops.vt_proj(xn, wv)                       # [B,C,Tpad]
             o = ops.attention(qk, qk, vt, B=B, H=H, Tq=T, Tk=T, d=d, ldq=2 * C, ldk=2 * C, q_off=0, k_off=C, scale=0.0)
         else:
-            wq = pk.get("wq", [self.to_q.weight], dt, lambda: pack_matrix(self.to_q.weight, dt))
-            wk = pk.get("wk", [self.to_k.weight], dt, lambda: pack_matrix(self.to_k.weight, dt))
+            wq = one(pk, R.matrix, self.to_q, dt)
+            wk = one(pk, R.matrix, self.to_k, dt)
             ehs = ctx.ehs
             Tk = ehs.shape[1]
             q = ops.linear(xn, wq, out_scale=cs)
@@ -262,18 +255,9 @@ class FeedForward(nn.Module):
         self._pk = PackCache()
 
     def forward(self, xn, residual):
-        dt = xn.dtype
-        pk = self._pk
-        proj, out = self.net[0].proj, self.net[2]
-        nh = proj.weight.shape[0] // 2
-
-        def build_in():
-            perm = geglu_perm(nh, proj.weight.device)
-            return pack_matrix(proj.weight, dt)[perm].contiguous(), f32(proj.bias)[perm].contiguous()
-
-        w_in, b_in = pk.get("in", [proj.weight, proj.bias], dt, build_in)
-        w_out = pk.get("wout", [out.weight], dt, lambda: pack_matrix(out.weight, dt))
-        b_out = pk.get("bout", [out.bias], dt, lambda: f32(out.bias))
+        dt, pk = xn.dtype, self._pk
+        w_in, b_in = one(pk, R.geglu, self.net[0].proj, dt)
+        w_out, b_out = one(pk, R.linear, self.net[2], dt)
         g = ops.linear(xn, w_in, b_in, act=ops.ACT_GEGLU)   # [B,T,4C]
         return ops.linear(g, w_out, b_out, res=residual, hilo=ops.PRECISE_RESIDUAL)
 
@@ -289,16 +273,13 @@ class BasicTransformerBlock(nn.Module):
         self.ff = FeedForward(dim)
         self._pk = PackCache()
 
-    def _ln(self, name, ln, dt):
-        return self._pk.get(name, [ln.weight, ln.bias], dt, lambda: (f32(ln.weight), f32(ln.bias)))
-
     def forward(self, x, ctx: Ctx):
         dt = x.dtype
-        g, b = self._ln("n1", self.norm1, dt)
+        g, b = one(self._pk, R.affine, self.norm1, dt)
         x = self.attn1(ops.layernorm(x, g, b, self.norm1.eps), ctx, x)
-        g, b = self._ln("n2", self.norm2, dt)
+        g, b = one(self._pk, R.affine, self.norm2, dt)
         x = self.attn2(ops.layernorm(x, g, b, self.norm2.eps), ctx, x)
-        g, b = self._ln("n3", self.norm3, dt)
+        g, b = one(self._pk, R.affine, self.norm3, dt)
         return self.ff(ops.layernorm(x, g, b, self.norm3.eps), x)
 
 
@@ -319,14 +300,11 @@ class Transformer2DModel(nn.Module):
         self._pk = PackCache()
 
     def forward(self, x, ctx: Ctx):
-        dt = x.dtype
-        pk = self._pk
+        dt, pk = x.dtype, self._pk
         B, H, W, Cc = x.shape
-        g, b = pk.get("n", [self.norm.weight, self.norm.bias], dt, lambda: (f32(self.norm.weight), f32(self.norm.bias)))
-        wi = pk.get("wi", [self.proj_in.weight], dt, lambda: pack_matrix(self.proj_in.weight, dt))
-        bi = pk.get("bi", [self.proj_in.bias], dt, lambda: f32(self.proj_in.bias))
-        wo = pk.get("wo", [self.proj_out.weight], dt, lambda: pack_matrix(self.proj_out.weight, dt))
-        bo = pk.get("bo", [self.proj_out.bias], dt, lambda: f32(self.proj_out.bias))
+        g, b = one(pk, R.affine, self.norm, dt)
+        wi, bi = one(pk, R.linear, self.proj_in, dt)
+        wo, bo = one(pk, R.linear, self.proj_out, dt)
         h = ops.groupnorm(x, g, b, self.norm.eps, groups=self.groups, silu=False)
         h = ops.linear(h.view(B, H * W, Cc), wi, bi, hilo=ops.PRECISE_RESIDUAL)
         for blk in self.transformer_blocks:
@@ -347,9 +325,7 @@ class Downsample2D(nn.Module):
 
     def forward(self, x):
         dt = x.dtype
-        w = self._pk.get("w", [self.conv.weight], dt,
-                         lambda: pack_conv3x3(self.conv.weight, dt, cblock=ops.conv_cblock(self.conv.weight.shape[1])))
-        b = self._pk.get("b", [self.conv.bias], dt, lambda: f32(self.conv.bias))
+        w, b = one(self._pk, R.conv3x3, self.conv, dt)
         return ops.conv3x3(x, w, b, stride=2, hilo=ops.PRECISE_RESIDUAL, cblock=ops.conv_cblock(x.shape[-1]))
 
 
@@ -363,9 +339,7 @@ class Upsample2D(nn.Module):
 
     def forward(self, x, output_size=None):
         dt = x.dtype
-        w = self._pk.get("w", [self.conv.weight], dt,
-                         lambda: pack_conv3x3(self.conv.weight, dt, cblock=ops.conv_cblock(self.conv.weight.shape[1])))
-        b = self._pk.get("b", [self.conv.bias], dt, lambda: f32(self.conv.bias))
+        w, b = one(self._pk, R.conv3x3, self.conv, dt)
         if output_size is not None and tuple(int(v) for v in output_size) != (2 * x.shape[1], 2 * x.shape[2]):
             # latent side not a multiple of 8 (controlnet.py:869-883, 1129-1130): F.interpolate(size=...), then the conv
             return ops.conv3x3(ops.resize_nearest(x, output_size), w, b, hilo=ops.PRECISE_RESIDUAL, cblock=ops.conv_cblock(x.shape[-1]))
@@ -379,28 +353,6 @@ def zero_module(m: nn.Module) -> nn.Module:
 
 
 # ---------------------------------------------------------------------------------------------------
-def pack_cond_conv3x3(weight: torch.Tensor, dtype, stride: int = 1, image: bool = False, bgr: bool = False) -> torch.Tensor:
-    """[Co, Ci, 3, 3] -> the weight image ``ops.cond_conv3x3`` reads (include/ur_kernels.h, ur_cond_conv3x3):
-    [Co / 16][Cp / CC][STEPS][64 lanes][8] with CC = ``ops.cond_conv_kchunk(Ci, stride, image)``, Cp = Ci rounded up to
-    CC, STEPS = ceil(9 * CC / 32); element j of lane l of step s holds k = 32 s + 8 (l // 16) + j = tap * CC + c of output
-    channel 16 nb + l % 16, zero where tap >= 9 or the channel is padding.  ``bgr``: the input-channel axis is flipped
-    here, so the kernel reads a BGR image as it lies in memory."""
-    co, ci = weight.shape[:2]
-    cc = ops.cond_conv_kchunk(ci, stride, image)
-    cp = _ceil(ci, cc)
-    steps = _ceil(9 * cc, 32) // 32
-    if co % 16:
-        raise ValueError("pack_cond_conv3x3: output channels are a multiple of 16")
-    w = weight.detach()
-    if bgr:
-        w = w.flip(1)
-    w = torch.nn.functional.pad(w.permute(0, 2, 3, 1).reshape(co, 9, ci), (0, cp - ci))  # [Co, tap, Cp]
-    w = w.reshape(co, 9, cp // cc, cc).permute(0, 2, 1, 3).reshape(co, cp // cc, 9 * cc)  # k = tap * CC + c per chunk
-    w = torch.nn.functional.pad(w, (0, steps * 32 - 9 * cc))
-    w = w.reshape(co // 16, 16, cp // cc, steps, 4, 8).permute(0, 2, 3, 4, 1, 5)            # lane = 16 * (k // 8 % 4) + n
-    return w.to(dtype).contiguous()
-
-
 class ControlNetConditioningEmbedding(nn.Module):
     """diffusers' ``ControlNetConditioningEmbedding`` (reference models/controlnet.py, ``controlnet_cond_embedding``):
     conv_in, then per level a stride-1 and a stride-2 3x3 conv, SiLU after each, and a zero-initialised conv_out; parameter
@@ -429,8 +381,6 @@ class ControlNetConditioningEmbedding(nn.Module):
         x = cond_nchw
         for i, conv in enumerate(convs):
             s, img = conv.stride[0], i == 0
-            w = self._pk.get(f"w{i}", [conv.weight], (dtype, bgr),
-                             lambda: pack_cond_conv3x3(conv.weight, dtype, s, image=img, bgr=bgr and img))
-            b = self._pk.get(f"b{i}", [conv.bias], dtype, lambda: f32(conv.bias))
+            w, b = one(self._pk, R.cond_conv3x3(img, bgr), conv, dtype)
             x = ops.cond_conv3x3(x, w, b, n_out=conv.out_channels, stride=s, act=ops.ACT_SILU, dtype=dtype, image=img)
         return x

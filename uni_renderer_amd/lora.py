@@ -3,8 +3,9 @@
 
 An adapter never becomes a second pair of GEMMs here: ``W + s * sum_adapters (alpha / rank) * weight * up @ down`` is
 written IN PLACE into the parameter by one grouped HIP launch per ``multi_max()`` (48) matrices (``ur_lora_merge_multi``,
-csrc/lora.hip) and the parameter's version counter is bumped, so every packed copy (``layers.PackCache``, the caches of
-``fused.py`` / ``graph.py``) and every captured graph (``pipeline._weights_signature``) is rebuilt on its next use.  The
+csrc/lora.hip) and the parameter's version counter is bumped, so every packed copy (one cache class, ``packs.PackCache``,
+valid for the versions of exactly the parameters its recipe reads: module forwards, grouped / hoisted step, VAE) and every captured
+graph (``graph.py``, ``pipeline._weights_signature``) is rebuilt on its next use.  The
 step keeps its launch count and its graph.
 
 The model keeps, per adapted parameter, one untouched copy (``base``, taken at the first merge), the fp32 factors on the

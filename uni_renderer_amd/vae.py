@@ -20,10 +20,14 @@ import torch.nn as nn
 
 from . import _lib, ops
 from ._lib import check
-from .layers import Conv2d, GroupNorm, Linear, PackCache, f32, pack_conv3x3, pack_matrix
+from . import packs as R
+from .layers import Conv2d, GroupNorm, Linear, PackCache
+from .packs import one
 from .modeling_utils import ConfigModelMixin, register_to_config
 
 CIN_PAD = 64
+_CONV_IN = R.conv3x3_padded(CIN_PAD)
+_POST_QUANT = R.linear_padded(CIN_PAD)  # 1x1 over the (zero padded) latent channels
 
 
 class _Resnet(nn.Module):
@@ -41,20 +45,16 @@ class _Resnet(nn.Module):
 
     def forward(self, x):
         dt, pk = x.dtype, self._pk
-        g1, b1 = pk.get("n1", [self.norm1.weight, self.norm1.bias], dt, lambda: (f32(self.norm1.weight), f32(self.norm1.bias)))
-        g2, b2 = pk.get("n2", [self.norm2.weight, self.norm2.bias], dt, lambda: (f32(self.norm2.weight), f32(self.norm2.bias)))
-        w1 = pk.get("w1", [self.conv1.weight], dt, lambda: pack_conv3x3(self.conv1.weight, dt))
-        c1 = pk.get("c1", [self.conv1.bias], dt, lambda: f32(self.conv1.bias))
+        g1, b1 = one(pk, R.affine, self.norm1, dt)
+        g2, b2 = one(pk, R.affine, self.norm2, dt)
+        w1, c1 = one(pk, R.conv3x3_tap, self.conv1, dt)
         h = ops.groupnorm(x, g1, b1, self.eps, groups=self.groups, silu=True)
         h = ops.conv3x3(h, w1, c1)
         h = ops.groupnorm(h, g2, b2, self.eps, groups=self.groups, silu=True)
         if self.conv_shortcut is not None:  # 1x1 shortcut rides in conv2's K loop (ur_igemm_desc.t0)
-            w2 = pk.get("w2s", [self.conv2.weight, self.conv_shortcut.weight], dt,
-                        lambda: torch.cat([pack_conv3x3(self.conv2.weight, dt), pack_matrix(self.conv_shortcut.weight, dt)], 1).contiguous())
-            c2 = pk.get("c2s", [self.conv2.bias, self.conv_shortcut.bias], dt, lambda: f32(self.conv2.bias) + f32(self.conv_shortcut.bias))
+            w2, c2 = one(pk, R.fold_tap, self, dt)
             return ops.conv3x3(h, w2, c2, tail=(x, None))
-        w2 = pk.get("w2", [self.conv2.weight], dt, lambda: pack_conv3x3(self.conv2.weight, dt))
-        c2 = pk.get("c2", [self.conv2.bias], dt, lambda: f32(self.conv2.bias))
+        w2, c2 = one(pk, R.conv3x3_tap, self.conv2, dt)
         return ops.conv3x3(h, w2, c2, res=x)
 
 
@@ -75,14 +75,10 @@ class _Attention(nn.Module):
         B, H, W, _ = x.shape
         T = H * W
         Tp = (T + 63) // 64 * 64
-        g, b = pk.get("gn", [self.group_norm.weight, self.group_norm.bias], dt, lambda: (f32(self.group_norm.weight), f32(self.group_norm.bias)))
-        wqk = pk.get("wqk", [self.to_q.weight, self.to_k.weight], dt,
-                     lambda: torch.cat([pack_matrix(self.to_q.weight, dt), pack_matrix(self.to_k.weight, dt)], 0).contiguous())
-        bqk = pk.get("bqk", [self.to_q.bias, self.to_k.bias], dt, lambda: torch.cat([f32(self.to_q.bias), f32(self.to_k.bias)]))
-        wv = pk.get("wv", [self.to_v.weight], dt, lambda: pack_matrix(self.to_v.weight, dt))
-        bv = pk.get("bv", [self.to_v.bias], dt, lambda: f32(self.to_v.bias))
-        wo = pk.get("wo", [self.to_out[0].weight], dt, lambda: pack_matrix(self.to_out[0].weight, dt))
-        bo = pk.get("bo", [self.to_out[0].bias], dt, lambda: f32(self.to_out[0].bias))
+        g, b = one(pk, R.affine, self.group_norm, dt)
+        wqk, bqk = one(pk, R.linear_rows, (self.to_q, self.to_k), dt)
+        wv, bv = one(pk, R.linear, self.to_v, dt)
+        wo, bo = one(pk, R.linear, self.to_out[0], dt)
         xn = ops.groupnorm(x, g, b, self.eps, groups=self.groups, silu=False).view(B, T, C)
         qk = ops.linear(xn, wqk, bqk)                      # [B, T, 2C] = q | k
         vt = ops.vt_proj(xn, wv)                           # [B, C, Tp] = (x Wv^T)^T without the bias (added below)
@@ -118,8 +114,7 @@ class _Down(nn.Module):
 
     def forward(self, x):
         dt = x.dtype
-        w = self._pk.get("w", [self.conv.weight], dt, lambda: pack_conv3x3(self.conv.weight, dt))
-        b = self._pk.get("b", [self.conv.bias], dt, lambda: f32(self.conv.bias))
+        w, b = one(self._pk, R.conv3x3_tap, self.conv, dt)
         return ops.conv3x3(x, w, b, stride=2, pad=0)
 
 
@@ -131,8 +126,7 @@ class _Up(nn.Module):
 
     def forward(self, x):
         dt = x.dtype
-        w = self._pk.get("w", [self.conv.weight], dt, lambda: pack_conv3x3(self.conv.weight, dt))
-        b = self._pk.get("b", [self.conv.bias], dt, lambda: f32(self.conv.bias))
+        w, b = one(self._pk, R.conv3x3_tap, self.conv, dt)
         return ops.conv3x3(x, w, b, ups=True)  # nearest-2x fused into the gather
 
 
@@ -263,24 +257,16 @@ class AutoencoderKL(ConfigModelMixin, nn.Module):
     @torch.no_grad()
     def encode(self, x: torch.Tensor, return_dict: bool = True):
         dt, pk, e = self._dt(), self._pk, self.encoder
-        w = pk.get("e.in", [e.conv_in.weight], dt, lambda: pack_conv3x3(e.conv_in.weight, dt, CIN_PAD))
-        b = pk.get("e.inb", [e.conv_in.bias], dt, lambda: f32(e.conv_in.bias))
+        w, b = one(pk, _CONV_IN, e.conv_in, dt)
         h = ops.conv3x3(ops.to_nhwc(x, dt, CIN_PAD), w, b)
         for lvl in e.down_blocks:
             h = lvl(h)
         h = e.mid_block(h)
-        g, gb = pk.get("e.no", [e.conv_norm_out.weight, e.conv_norm_out.bias], dt, lambda: (f32(e.conv_norm_out.weight), f32(e.conv_norm_out.bias)))
+        g, gb = one(pk, R.affine, e.conv_norm_out, dt)
         h = ops.groupnorm(h, g, gb, e.conv_norm_out.eps, groups=e.conv_norm_out.num_groups, silu=True)
-        # quant_conv (1x1, per pixel) composed with conv_out on the host in fp32: quant(conv(h)) = (Wq Wc) * h + (Wq bc + bq)
+        # quant_conv (1x1, per pixel) composed with conv_out on the host in fp32 (packs.vae_moments)
         q = self.quant_conv
-
-        def compose():
-            wq = q.weight.detach().float().reshape(q.weight.shape[0], -1)
-            wc = torch.einsum("oi,icyx->ocyx", wq, e.conv_out.weight.detach().float())
-            bc = wq @ e.conv_out.bias.detach().float() + q.bias.detach().float()
-            return pack_conv3x3(wc, dt), bc.contiguous()
-
-        wc, bc = pk.get("e.out", [e.conv_out.weight, e.conv_out.bias, q.weight, q.bias], dt, compose)
+        wc, bc = one(pk, R.vae_moments, self, dt)
         moments = ops.to_nchw(ops.conv3x3(h, wc, bc, n_out=q.weight.shape[0]), x.dtype if x.dtype in (torch.float16, torch.bfloat16, torch.float32) else torch.float32)
         post = DiagonalGaussianDistribution(moments)
         return AutoencoderKLOutput(latent_dist=post) if return_dict else (post,)
@@ -292,21 +278,18 @@ class AutoencoderKL(ConfigModelMixin, nn.Module):
         pq = self.post_quant_conv
         B, Cz, H, W = z.shape
         # post_quant_conv: 1x1 over the (zero padded to 64) latent channels, output again 64 wide for conv_in
-        wp = pk.get("d.pq", [pq.weight], dt, lambda: torch.nn.functional.pad(pack_matrix(pq.weight, dt), (0, CIN_PAD - Cz)).contiguous())
-        bp = pk.get("d.pqb", [pq.bias], dt, lambda: f32(pq.bias))
+        wp, bp = one(pk, _POST_QUANT, pq, dt)
         zin = ops.to_nhwc(z, dt, CIN_PAD)
         zq = torch.empty(B, H, W, CIN_PAD, dtype=dt, device=z.device)
         ops.igemm(x0=zin, w=wp, out=zq, M=B * H * W, N=pq.weight.shape[0], K=CIN_PAD, c0=CIN_PAD, ldx0=CIN_PAD, ldw=CIN_PAD,
                   ldc=CIN_PAD, n_store=CIN_PAD, bias=bp)
-        w = pk.get("d.in", [d.conv_in.weight], dt, lambda: pack_conv3x3(d.conv_in.weight, dt, CIN_PAD))
-        b = pk.get("d.inb", [d.conv_in.bias], dt, lambda: f32(d.conv_in.bias))
+        w, b = one(pk, _CONV_IN, d.conv_in, dt)
         h = d.mid_block(ops.conv3x3(zq, w, b))
         for lvl in d.up_blocks:
             h = lvl(h)
-        g, gb = pk.get("d.no", [d.conv_norm_out.weight, d.conv_norm_out.bias], dt, lambda: (f32(d.conv_norm_out.weight), f32(d.conv_norm_out.bias)))
+        g, gb = one(pk, R.affine, d.conv_norm_out, dt)
         h = ops.groupnorm(h, g, gb, d.conv_norm_out.eps, groups=d.conv_norm_out.num_groups, silu=True)
-        wo = pk.get("d.out", [d.conv_out.weight], dt, lambda: pack_conv3x3(d.conv_out.weight, dt))
-        bo = pk.get("d.outb", [d.conv_out.bias], dt, lambda: f32(d.conv_out.bias))
+        wo, bo = one(pk, R.conv3x3_tap, d.conv_out, dt)
         img = ops.to_nchw(ops.conv3x3(h, wo, bo, n_out=d.conv_out.weight.shape[0]), z.dtype if z.dtype in (torch.float16, torch.bfloat16, torch.float32) else torch.float32)
         return DecoderOutput(sample=img) if return_dict else (img,)
 
