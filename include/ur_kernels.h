@@ -36,6 +36,9 @@
  *                   (models/unet_2d_blocks.py:2343-2370, 2522-2546, 2653-2677, 2767-2790): the in-place backbone scale
  *                   `hidden[:, : C // 2] *= b` and fourier_filter's fftn -> fftshift -> box * s -> ifftshift -> ifftn -> real
  *                   of the skip, as one launch without an FFT.
+ *   ur_blend_tiles  the stitch of diffusers' AutoencoderKL.tiled_decode / tiled_encode behind enable_vae_tiling
+ *                   (models/pipeline.py:200-215): blend_v / blend_h over the tile grid, the crops and the two torch.cat, as one
+ *                   launch that also converts NHWC to NCHW.
  */
 #ifndef UR_KERNELS_H
 #define UR_KERNELS_H
@@ -436,6 +439,41 @@ int ur_lora_merge_multi(const int64_t* items, int n, int dtype, void* stream);
 int ur_lora_multi_max(void);
 int ur_lora_max_rank(void);
 int ur_lora_item_words(void);
+
+/*
+ * The stitch of a tiled VAE decode / encode in ONE launch (an addition to ABI 17; csrc/vaetile.hip): what diffusers 0.24's
+ * AutoencoderKL.tiled_decode / tiled_encode do after the network calls -- blend_v and blend_h (two Python loops of `blend`
+ * small strided ops per tile), the crop to `limit` and two torch.cat -- behind UniRendererPipeline.enable_vae_tiling
+ * (models/pipeline.py:200-215), with the NHWC -> NCHW conversion of ur_nhwc_to_nchw fused in.
+ *   items   a HOST table of four int64_t words per tile, [(above + rows) * cols][4] = { address, sample stride in elements, h, w },
+ *           row-major over the grid: tile (i, j) is an NHWC tensor [B][h_i][w_j][C] in `tile_dtype` (UR_DT_F16 / BF16), pixels
+ *           contiguous, sample b at address + b * stride (a tile may be a slice of a batched tensor).  h depends on the tile row
+ *           only and w on the tile column only.  The entry width and the most tiles one launch takes, the row above included,
+ *           are host calls: ur_blend_tiles_item_words() and ur_blend_tiles_max().
+ *   above   1: the first row of the table is the tile row ABOVE the ones stitched here: read for the vertical blend, never
+ *           written out.  How a grid with more tiles than one launch takes is stitched in bands of tile rows.
+ *   out     [B][C][Hout][Wout] in `out_dtype` (UR_DT_F16 / BF16 / F32), channel planes out_plane >= Hout * Wout elements apart
+ *           and samples C * out_plane apart (a band: out = the first row of the band inside the whole tensor, out_plane the
+ *           whole tensor's).  Tile (i, j) contributes its first min(limit, h_i) x min(limit, w_j) pixels; Hout and Wout are the
+ *           sums of those extents over the `rows` rows and `cols` columns.
+ * Semantics: diffusers' sequential IN-PLACE stitch.  Tiles are visited row by row, left to right; blend_v(above, tile) first,
+ * then blend_h(left, tile); both write `tile`, and the neighbour they read has been blended already.  Vertical: e =
+ * min(h_above, h_tile, blend) and tile[y] = above[h_above - e + y] * (1 - y / e) + tile[y] * (y / e) for y < e; horizontal the same
+ * along x.  So the corner y < e_v, x < e_h of a tile is a blend of FOUR raw tiles (the tile above was blended with its own left
+ * neighbour before it was read), not of the two raw neighbours.  Every output element is computed from the raw tiles in fp32 --
+ * w = y / e as an fp32 quotient, a (1 - w) + b w as fma(b, w, a * (1 - w)), nested in the order above -- and rounded once.  No
+ * atomics; deterministic.  That closed form needs the rows / columns a tile hands to its successor to be untouched by its own
+ * blends: every tile row / column that has a successor must be at least 2 * blend long (tile_overlap_factor <= 1 / 3; diffusers'
+ * default is 0.25), else UR_E_UNSUPPORTED.
+ * C = 1 .. 8 (3: images, 8: posterior moments); a larger C, more than ur_blend_tiles_max() tiles, Hout or B over 65535:
+ * UR_E_UNSUPPORTED.  Before any launch: a null or misaligned address, rows < 1, cols < 1, above not 0 / 1, B < 1, C < 1,
+ * blend < 0, limit < 1, a negative sample stride, a tile shorter than one pixel, h / w that differ along a row / column, Hout /
+ * Wout that are not the sums, out_plane < Hout * Wout or an unknown dtype: UR_E_BADARG.
+ */
+int ur_blend_tiles(const int64_t* items, int rows, int cols, int above, int B, int C, int blend, int limit, void* out, int Hout,
+                   int Wout, int64_t out_plane, int tile_dtype, int out_dtype, void* stream);
+int ur_blend_tiles_max(void);
+int ur_blend_tiles_item_words(void);
 
 /* Sinusoidal timestep embedding of nt (1 or B) fp32 timesteps: out[b][:] = [cos | sin] (flip) or
  * [sin | cos]; fp32 math. */

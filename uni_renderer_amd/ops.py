@@ -986,6 +986,67 @@ def to_nchw(x_nhwc: torch.Tensor, dtype=None) -> torch.Tensor:
     return out
 
 
+BLEND_ITEM_WORDS = 4  # int64_t words per tile of ur_blend_tiles' table: address, sample stride (elements), h, w
+
+
+def blend_tiles_max() -> int:
+    """Tiles per launch of ``ur_blend_tiles``, a read-only row above included (the library's ``ur_blend_tiles_max``)."""
+    return int(_lib.load().ur_blend_tiles_max())
+
+
+def blend_tiles(tiles, blend: int, limit: int, dtype=None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The stitch of diffusers' ``tiled_decode`` / ``tiled_encode`` (``ur_blend_tiles``): ``tiles[i][j]`` is the NHWC tile
+    ``[B, h_i, w_j, C]`` (fp16 / bf16; a slice along the batch of a larger tensor is fine) of grid row ``i``, column ``j``;
+    returns the contiguous NCHW ``[B, C, sum_i min(limit, h_i), sum_j min(limit, w_j)]`` in ``dtype`` (default: the tiles')
+    with the sequential in-place ``blend_v`` / ``blend_h`` of extent ``blend`` applied.  One launch; a grid with more tiles
+    than one launch takes is stitched in bands of tile rows, the row above each band passed along read-only.  ``out``: a
+    contiguous tensor of that shape to write instead of a fresh one."""
+    rows, cols = len(tiles), len(tiles[0]) if tiles else 0
+    if rows < 1 or cols < 1 or any(len(r) != cols for r in tiles):
+        raise ValueError("blend_tiles: tiles is a non-empty rectangular list of lists")
+    first = tiles[0][0]
+    _require_gpu(first)
+    lib = _lib.load()
+    if lib.ur_blend_tiles_item_words() != BLEND_ITEM_WORDS:
+        raise _lib.UrLibraryError(f"ur_blend_tiles takes {lib.ur_blend_tiles_item_words()} words per tile, this package writes {BLEND_ITEM_WORDS}")
+    B, _, _, Cc = first.shape
+    dtype = (first.dtype if out is None else out.dtype) if dtype is None else dtype
+    hs, ws = [r[0].shape[1] for r in tiles], [t.shape[2] for t in tiles[0]]
+    for i, r in enumerate(tiles):
+        for j, t in enumerate(r):
+            if t.dtype != first.dtype or t.device != first.device or tuple(t.shape) != (B, hs[i], ws[j], Cc):
+                raise ValueError(f"blend_tiles: tile ({i}, {j}) is {tuple(t.shape)} {t.dtype}, expected {(B, hs[i], ws[j], Cc)} {first.dtype}")
+            if t.stride()[1:] != (ws[j] * Cc, Cc, 1):
+                raise ValueError(f"blend_tiles: tile ({i}, {j}) must have contiguous NHWC samples (strides {t.stride()})")
+    if blend > 0 and (any(h < 2 * blend for h in hs[:-1]) or any(w < 2 * blend for w in ws[:-1])):
+        raise NotImplementedError("blend_tiles: every tile that has a successor must be at least 2 * blend long "
+                                  "(tile_overlap_factor <= 1/3)")
+    kh, Wout = [min(limit, h) for h in hs], sum(min(limit, w) for w in ws)
+    Hout = sum(kh)
+    if out is None:
+        out = torch.empty(B, Cc, Hout, Wout, dtype=dtype, device=first.device)
+    elif tuple(out.shape) != (B, Cc, Hout, Wout) or out.dtype != dtype or out.device != first.device or not out.is_contiguous():
+        raise ValueError(f"blend_tiles: out must be a contiguous {(B, Cc, Hout, Wout)} {dtype} tensor on {first.device}")
+    nmax = blend_tiles_max()
+    if 2 * cols > nmax:
+        raise NotImplementedError(f"blend_tiles: {cols} tile columns; one launch takes {nmax} tiles and needs two rows of them")
+    e0 = _prof_begin()
+    r0, y0 = 0, 0
+    while r0 < rows:
+        above = 1 if r0 > 0 else 0
+        r1 = min(rows, r0 + nmax // cols - above)
+        band = [t for r in tiles[r0 - above:r1] for t in r]
+        table = (C.c_int64 * (BLEND_ITEM_WORDS * len(band)))(
+            *(int(v) for t in band for v in (t.data_ptr(), t.stride(0) if B > 1 else 0, t.shape[1], t.shape[2])))
+        check(lib.ur_blend_tiles(table, r1 - r0, cols, above, B, Cc, int(blend), int(limit),
+                                 out.data_ptr() + y0 * Wout * out.element_size(), sum(kh[r0:r1]), Wout, Hout * Wout,
+                                 DT[first.dtype], DT_ANY[dtype], _stream()), "ur_blend_tiles")
+        y0 += sum(kh[r0:r1])
+        r0 = r1
+    _prof_end(e0, "blend_tiles", 0.0, float(out.numel() * (out.element_size() + first.element_size())))
+    return out
+
+
 def as_nchw_view(x_nhwc: torch.Tensor) -> torch.Tensor:
     """Zero-copy logical-NCHW view of an NHWC tensor (channels_last strides); the low part of a (hi, lo) pair stays
     attached (as the same kind of view)."""

@@ -103,6 +103,25 @@ class UniRendererPipeline:
         """ref 762-764."""
         self.unet.disable_freeu()
 
+    # ---- VAE slicing / tiling (ref 185-215): the VAE's own switches ---------------------------------------
+    def enable_vae_slicing(self):
+        """The VAE encodes / decodes a batch one sample at a time (ref 185-190)."""
+        self.vae.enable_slicing()
+
+    def disable_vae_slicing(self):
+        """ref 193-198."""
+        self.vae.disable_slicing()
+
+    def enable_vae_tiling(self):
+        """The VAE processes inputs larger than its tile size as overlapping tiles, stitched by one fused launch
+        (``AutoencoderKL.enable_tiling``; ref 201-207).  Tiling changes the images, as in the reference: every tile has its
+        own GroupNorm statistics and attention."""
+        self.vae.enable_tiling()
+
+    def disable_vae_tiling(self):
+        """ref 210-215."""
+        self.vae.disable_tiling()
+
     # ---- LoRA (the reference's LoraLoaderMixin, UNet part) ----------------------------------------------
     def load_lora_weights(self, pretrained_model_name_or_path_or_dict, weight_name=None, adapter_name: str = "default", **kwargs):
         """Loads a LoRA file (a state dict, a ``.safetensors`` file or a directory holding ``weight_name``; local files only)

@@ -30,6 +30,45 @@ _CONV_IN = R.conv3x3_padded(CIN_PAD)
 _POST_QUANT = R.linear_padded(CIN_PAD)  # 1x1 over the (zero padded) latent channels
 
 
+@dataclass(frozen=True)
+class TileAxis:
+    """One axis of a tile grid: per tile its start and length on the input, its length on the output, the extent of the
+    blend with its predecessor (0 for the first tile) and how much of it is kept; ``blend`` / ``limit`` as diffusers names
+    them (``blend_extent`` / ``row_limit``)."""
+    positions: Tuple[int, ...]
+    lengths: Tuple[int, ...]
+    out_lengths: Tuple[int, ...]
+    extents: Tuple[int, ...]
+    kept: Tuple[int, ...]
+    blend: int
+    limit: int
+
+
+def tile_axis(length: int, tile_in: int, tile_out: int, factor: float, out_len) -> TileAxis:
+    """The tiles diffusers 0.24 cuts along one axis of ``length`` (pure Python, no device): tiles of ``tile_in`` starting
+    every ``overlap = int(tile_in * (1 - factor))``, each ``out_len(n)`` long on the output side, blended over ``blend =
+    int(tile_out * factor)`` and cropped to ``limit = tile_out - blend``.  ``tiled_decode``: ``tile_in`` = the latent tile,
+    ``tile_out`` = the sample tile, ``out_len`` = times the scale; ``tiled_encode`` is the mirror image (steps in pixels,
+    blends in latents).  The fused stitch evaluates the sequential in-place blends as a closed form over the raw tiles,
+    which holds while a tile's own blends stay clear of what it hands to its successor: ``NotImplementedError`` for a
+    factor above 1/3 or a tile with a successor shorter than ``2 * blend``."""
+    if not 0.0 <= factor <= 1.0 / 3.0:
+        raise NotImplementedError(f"tile_overlap_factor = {factor}: the fused tile stitch supports 0 <= factor <= 1/3 (diffusers' default: 0.25)")
+    overlap, blend = int(tile_in * (1 - factor)), int(tile_out * factor)
+    limit = tile_out - blend
+    if length < 1 or overlap < 1 or limit < 1:
+        raise ValueError(f"tile_axis: nothing to cut (length {length}, tile {tile_in} -> {tile_out}, factor {factor})")
+    positions = tuple(range(0, length, overlap))
+    lengths = tuple(min(tile_in, length - p) for p in positions)
+    out_lengths = tuple(out_len(n) for n in lengths)
+    if min(out_lengths) < 1:
+        raise ValueError(f"tile_axis: a tile of {lengths[out_lengths.index(min(out_lengths))]} has no output (length {length}, tile {tile_in})")
+    if blend > 0 and any(n < 2 * blend for n in out_lengths[:-1]):
+        raise NotImplementedError(f"tile_axis: a tile with a successor is shorter than 2 * blend = {2 * blend} (output lengths {out_lengths})")
+    extents = (0,) + tuple(min(a, b, blend) for a, b in zip(out_lengths, out_lengths[1:]))
+    return TileAxis(positions, lengths, out_lengths, extents, tuple(min(limit, n) for n in out_lengths), blend, limit)
+
+
 class _Resnet(nn.Module):
     """diffusers ResnetBlock2D with ``temb_channels=None`` (no time embedding), eps 1e-6."""
 
@@ -225,6 +264,12 @@ class AutoencoderKL(ConfigModelMixin, nn.Module):
         self.post_quant_conv = Conv2d(latent_channels, latent_channels, 1)
         self.compute_dtype: Optional[torch.dtype] = None
         self._pk = PackCache()
+        # diffusers' tiling / slicing state, with its definitions (AutoencoderKL.__init__)
+        self.use_slicing = False
+        self.use_tiling = False
+        self.tile_sample_min_size = sample_size[0] if isinstance(sample_size, (list, tuple)) else sample_size
+        self.tile_latent_min_size = int(self.tile_sample_min_size / (2 ** (len(boc) - 1)))
+        self.tile_overlap_factor = 0.25
 
     _DEPRECATED_ATTN = {"query": "to_q", "key": "to_k", "value": "to_v", "proj_attn": "to_out.0"}
 
@@ -253,9 +298,99 @@ class AutoencoderKL(ConfigModelMixin, nn.Module):
                                "torch.autocast, or set vae.compute_dtype")
         return dt
 
+    @staticmethod
+    def _io_dtype(t: torch.Tensor) -> torch.dtype:
+        return t.dtype if t.dtype in (torch.float16, torch.bfloat16, torch.float32) else torch.float32
+
+    # ---- tiling and slicing (diffusers AutoencoderKL.enable_tiling / enable_slicing; pipeline.py:185-215) -----------
+    def enable_tiling(self, use_tiling: bool = True):
+        """Inputs larger than ``tile_sample_min_size`` (``encode``) / ``tile_latent_min_size`` (``decode``) are processed
+        as overlapping tiles stitched by one ``ur_blend_tiles`` launch.  The result differs from the plain path the way
+        diffusers' does: every tile has its own GroupNorm statistics and mid-block attention.  Not supported:
+        ``tile_overlap_factor`` above 1/3 (``NotImplementedError``), graph capture and autograd of the tiled paths, and
+        ``blend_v`` / ``blend_h`` as methods.  Tiles of one shape run as one batch, so peak memory is that of the plain
+        path (profiles/vae_tiling_ab.txt)."""
+        self.use_tiling = use_tiling
+
+    def disable_tiling(self):
+        self.enable_tiling(False)
+
+    def enable_slicing(self):
+        """Batches are encoded / decoded one sample at a time and concatenated."""
+        self.use_slicing = True
+
+    def disable_slicing(self):
+        self.use_slicing = False
+
+    def _latent_len(self, n: int) -> int:
+        """Latent length of ``n`` pixels: one (0, 1)-padded stride-2 3x3 conv per encoder level but the last."""
+        for _ in range(len(self.config.block_out_channels) - 1):
+            n = (n - 2) // 2 + 1
+        return n
+
+    def _tile_axes(self, height: int, width: int, decode: bool):
+        scale = 2 ** (len(self.config.block_out_channels) - 1)
+        if decode:
+            tin, tout, out_len = self.tile_latent_min_size, self.tile_sample_min_size, lambda n: n * scale
+        else:
+            tin, tout, out_len = self.tile_sample_min_size, self.tile_latent_min_size, self._latent_len
+        return tuple(tile_axis(n, tin, tout, self.tile_overlap_factor, out_len) for n in (height, width))
+
+    def _tiled(self, x: torch.Tensor, decode: bool) -> torch.Tensor:
+        """The network over the tiles of NCHW ``x`` and the stitch: one ``ur_blend_tiles`` launch."""
+        tiles, blend, limit = self._network_tiles(x, decode)
+        return ops.blend_tiles(tiles, blend, limit, self._io_dtype(x))
+
+    def _network_tiles(self, x: torch.Tensor, decode: bool):
+        """``(tiles, blend, limit)``: the NHWC network outputs ``tiles[i][j]`` of the tile grid over NCHW ``x``.  Tiles of one
+        shape run as ONE batch, tile-major, the way ``num_images_per_prompt`` folds repeats (a 1024 x 1024 decode: four
+        network calls for 4 + 2 + 2 + 1 tiles), so a tile is a slice along the batch of its group's output."""
+        net = self._decode_nhwc if decode else self._encode_nhwc
+        B = x.shape[0]
+        ay, ax = self._tile_axes(x.shape[2], x.shape[3], decode)
+        groups = {}
+        for i, (py, ly) in enumerate(zip(ay.positions, ay.lengths)):
+            for j, (px, lx) in enumerate(zip(ax.positions, ax.lengths)):
+                groups.setdefault((ly, lx), []).append((i, j, py, px))
+        tiles = [[None] * len(ax.positions) for _ in ay.positions]
+        for (ly, lx), members in groups.items():
+            views = [x[:, :, py:py + ly, px:px + lx] for _, _, py, px in members]
+            y = net(views[0] if len(views) == 1 else torch.cat(views, 0))
+            for k, (i, j, _, _) in enumerate(members):
+                tiles[i][j] = y[k * B:(k + 1) * B]
+        return tiles, ay.blend, ay.limit
+
+    @torch.no_grad()
+    def tiled_encode(self, x: torch.Tensor, return_dict: bool = True):
+        """diffusers 0.24 ``tiled_encode``: tiles of ``tile_sample_min_size`` pixels stepping by ``int(tile_sample_min_size *
+        (1 - tile_overlap_factor))``, their 8-channel moments blended over ``int(tile_latent_min_size * tile_overlap_factor)``
+        latents; the posterior is built from the blended moments."""
+        post = DiagonalGaussianDistribution(self._tiled(x, False))
+        return AutoencoderKLOutput(latent_dist=post) if return_dict else (post,)
+
+    @torch.no_grad()
+    def tiled_decode(self, z: torch.Tensor, return_dict: bool = True):
+        """diffusers 0.24 ``tiled_decode``: tiles of ``tile_latent_min_size`` latents stepping by ``int(tile_latent_min_size *
+        (1 - tile_overlap_factor))``, the decoded images blended over ``int(tile_sample_min_size * tile_overlap_factor)``
+        pixels."""
+        img = self._tiled(z, True)
+        return DecoderOutput(sample=img) if return_dict else (img,)
+
     # ---- encode (train.py:1266-1304; pipeline.py:2533-2538) ---------------------------------------------------------
     @torch.no_grad()
     def encode(self, x: torch.Tensor, return_dict: bool = True):
+        if self.use_tiling and (x.shape[-1] > self.tile_sample_min_size or x.shape[-2] > self.tile_sample_min_size):
+            return self.tiled_encode(x, return_dict=return_dict)
+        dt = self._io_dtype(x)
+        if self.use_slicing and x.shape[0] > 1:
+            moments = torch.cat([ops.to_nchw(self._encode_nhwc(s), dt) for s in x.split(1)])
+        else:
+            moments = ops.to_nchw(self._encode_nhwc(x), dt)
+        post = DiagonalGaussianDistribution(moments)
+        return AutoencoderKLOutput(latent_dist=post) if return_dict else (post,)
+
+    def _encode_nhwc(self, x: torch.Tensor) -> torch.Tensor:
+        """The posterior moments of NCHW ``x`` as the network leaves them: NHWC ``[B, h, w, 2 * latent_channels]``."""
         dt, pk, e = self._dt(), self._pk, self.encoder
         w, b = one(pk, _CONV_IN, e.conv_in, dt)
         h = ops.conv3x3(ops.to_nhwc(x, dt, CIN_PAD), w, b)
@@ -267,13 +402,24 @@ class AutoencoderKL(ConfigModelMixin, nn.Module):
         # quant_conv (1x1, per pixel) composed with conv_out on the host in fp32 (packs.vae_moments)
         q = self.quant_conv
         wc, bc = one(pk, R.vae_moments, self, dt)
-        moments = ops.to_nchw(ops.conv3x3(h, wc, bc, n_out=q.weight.shape[0]), x.dtype if x.dtype in (torch.float16, torch.bfloat16, torch.float32) else torch.float32)
-        post = DiagonalGaussianDistribution(moments)
-        return AutoencoderKLOutput(latent_dist=post) if return_dict else (post,)
+        return ops.conv3x3(h, wc, bc, n_out=q.weight.shape[0])
 
     # ---- decode (pipeline.py:2755-2769) -----------------------------------------------------------------------------
     @torch.no_grad()
     def decode(self, z: torch.Tensor, return_dict: bool = True, generator=None):
+        if self.use_slicing and z.shape[0] > 1:
+            img = torch.cat([self._decode(s) for s in z.split(1)])
+        else:
+            img = self._decode(z)
+        return DecoderOutput(sample=img) if return_dict else (img,)
+
+    def _decode(self, z: torch.Tensor) -> torch.Tensor:
+        if self.use_tiling and (z.shape[-1] > self.tile_latent_min_size or z.shape[-2] > self.tile_latent_min_size):
+            return self.tiled_decode(z, return_dict=False)[0]
+        return ops.to_nchw(self._decode_nhwc(z), self._io_dtype(z))
+
+    def _decode_nhwc(self, z: torch.Tensor) -> torch.Tensor:
+        """The image of NCHW latents ``z`` as the network leaves it: NHWC ``[B, H, W, out_channels]``."""
         dt, pk, d = self._dt(), self._pk, self.decoder
         pq = self.post_quant_conv
         B, Cz, H, W = z.shape
@@ -290,8 +436,7 @@ class AutoencoderKL(ConfigModelMixin, nn.Module):
         g, gb = one(pk, R.affine, d.conv_norm_out, dt)
         h = ops.groupnorm(h, g, gb, d.conv_norm_out.eps, groups=d.conv_norm_out.num_groups, silu=True)
         wo, bo = one(pk, R.conv3x3_tap, d.conv_out, dt)
-        img = ops.to_nchw(ops.conv3x3(h, wo, bo, n_out=d.conv_out.weight.shape[0]), z.dtype if z.dtype in (torch.float16, torch.bfloat16, torch.float32) else torch.float32)
-        return DecoderOutput(sample=img) if return_dict else (img,)
+        return ops.conv3x3(h, wo, bo, n_out=d.conv_out.weight.shape[0])
 
     def forward(self, sample: torch.Tensor, sample_posterior: bool = False, return_dict: bool = True, generator=None):
         post = self.encode(sample).latent_dist
