@@ -440,6 +440,32 @@ int ur_lora_multi_max(void);
 int ur_lora_max_rank(void);
 int ur_lora_item_words(void);
 
+/* The same merge with `base` read in base_dtype and `w` written in out_dtype (the fp32 master weights of a LoRA training
+ * step merged straight into the compute-dtype operand; an addition to ABI 17).  Items, limits, arithmetic and argument
+ * checks are those of ur_lora_merge_multi (alignment per side: base to base_dtype, w to out_dtype): the ascending fma
+ * chain, one fma(scale, acc, base), ONE rounding to out_dtype.  base_dtype == out_dtype is ur_lora_merge_multi bit for bit
+ * (one kernel body).  With different dtypes R == 0 converts the values of base. */
+int ur_lora_merge_cast_multi(const int64_t* items, int n, int base_dtype, int out_dtype, void* stream);
+
+/* The gradients of the factors from the gradient of the merged weight, over a list of matrices in ONE launch (an addition
+ * to ABI 17; csrc/lora.hip).  Per item
+ *     d_up[n][r]   = scale * rscale[r] * sum_k dw[n][k] * down[r][k]
+ *     d_down[r][k] = scale * rscale[r] * sum_n up[n][r] * dw[n][k]
+ * items: a HOST table of ur_lora_grad_item_words() (ten) int64_t words per item,
+ * { dw, up, down, rscale, d_up, d_down, N, K, R, scale }: six device addresses (rscale may be 0: ones), three counts and the
+ * IEEE bits of the fp32 `scale` in the low half of the last word.  At most ur_lora_multi_max() items per launch.
+ * dw: [N][K] row-major in dw_dtype (UR_DT_F16, UR_DT_BF16 or UR_DT_F32: what ur_wgrad wrote), element aligned.  up fp32
+ * [N][R], down fp32 [R][K], rscale fp32 [R]; d_up fp32 [N][R] and d_down fp32 [R][K] are WRITTEN (not accumulated into).
+ * Contract: fp32 accumulation with fma; every sum runs in an order that is a fixed function of (N, K, R) only -- no
+ * atomics, no dependence on the other items of the launch, on their order or on the grid -- so results are bit-reproducible;
+ * fl(scale * rscale[r]) multiplies the finished sum.  Any N, K >= 1 (below 2^31), 1 <= R <= ur_lora_max_rank().  Rows or
+ * addresses that do not allow the 4-element access take an element-wise path; no access is wider than its alignment.
+ * Before any launch: a null dw / up / down / d_up / d_down, a misaligned address, N <= 0, K <= 0, R <= 0, an unknown
+ * dtype, n outside 1 .. ur_lora_multi_max(), or d_up / d_down overlapping an input or each other: UR_E_BADARG; R over the
+ * rank limit or more workgroups than one grid holds: UR_E_UNSUPPORTED. */
+int ur_lora_grad_multi(const int64_t* items, int n, int dw_dtype, void* stream);
+int ur_lora_grad_item_words(void);
+
 /*
  * The stitch of a tiled VAE decode / encode in ONE launch (an addition to ABI 17; csrc/vaetile.hip): what diffusers 0.24's
  * AutoencoderKL.tiled_decode / tiled_encode do after the network calls -- blend_v and blend_h (two Python loops of `blend`

@@ -54,6 +54,11 @@ def main():
                     "(train/train.py:1073-1074): the resnets of the flagged blocks are recomputed in the backward")
     ap.add_argument("--accumulate-into-buckets", action="store_true", help="round-5 gradient protocol (zero the flat buckets, autograd "
                     "adds every gradient into them) instead of round 6's direct writes (backward.GradSink): A/B runs")
+    ap.add_argument("--lora-rank", type=int, default=0, help="train a LoRA adapter of this rank on the UNet (add_adapter): the UNet's "
+                    "own parameters are frozen and the optimizer is built over the parameters that require a gradient")
+    ap.add_argument("--lora-targets", default="attn", choices=["attn", "attn+ff"], help="the adapted modules: the attention "
+                    "projections, or those and the feed-forward matrices")
+    ap.add_argument("--freeze-exchange-nets", action="store_true", help="with --lora-rank: freeze the encoder and the decoder too")
     args = ap.parse_args()
     world, rank, local = (int(os.environ.get(k, d)) for k, d in (("WORLD_SIZE", "1"), ("RANK", "0"), ("LOCAL_RANK", "0")))
     if args.gpus > 1 and world == 1 and "RANK" not in os.environ:
@@ -79,7 +84,17 @@ def main():
                  t_img=torch.randint(0, 1000, (B,), device=dev, generator=g),
                  t_attr=torch.randint(0, 1000, (B,), device=dev, generator=g),
                  target_img=mk(B, 4, L, L), target_attr=mk(B, 28, L, L))
-    params = [p for m in nets for p in m.parameters()]
+    if args.lora_rank:
+        targets = ("to_q", "to_k", "to_v", "to_out.0") + (("ff.net.0.proj", "ff.net.2") if args.lora_targets == "attn+ff" else ())
+        nets[0].requires_grad_(False)
+        nets[0].add_adapter(rank=args.lora_rank, target_modules=targets, generator=torch.Generator().manual_seed(11))
+        with torch.no_grad():  # up = 0 would leave d_down identically zero: time a step whose factor gradients are live
+            for p in nets[0].lora_parameters()[1::2]:
+                p.normal_(0.0, 1e-3)
+        if args.freeze_exchange_nets:
+            for m in nets[1:]:
+                m.requires_grad_(False)
+    params = [p for m in nets for p in m.parameters() if p.requires_grad]
     if args.torch_adamw:
         opt = torch.optim.AdamW(params, lr=1e-5, fused=True, capturable=args.graph)
     elif args.adamw8bit:
@@ -128,6 +143,9 @@ def main():
                               grad_sync=(dict(algorithm=args.algorithm, comm_dtype=args.comm_dtype, overlap=not args.no_overlap,
                                               buckets=len(buckets.buckets), launched_during_backward=buckets.launched_from_hooks)
                                          if buckets is not None else None), peak_mem_gb=round(torch.cuda.max_memory_allocated() / 2**30, 1),
+                              lora=(dict(rank=args.lora_rank, targets=args.lora_targets, matrices=len(nets[0].lora_parameters()) // 2,
+                                         frozen_exchange_nets=bool(args.freeze_exchange_nets)) if args.lora_rank else None),
+                              trainable_params=sum(p.numel() for p in params),
                               wgrad_queue=_queue_stats(), phase_ms=(phases if args.graph else None))))
     if world > 1 or args.force_collectives:
         torch.distributed.barrier()

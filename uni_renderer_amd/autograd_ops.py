@@ -49,7 +49,7 @@ class Linear(Function):
     def forward(ctx, x, w, b, res, rowadd, rows_per_b):
         ctx.save_for_backward(x, w)
         ctx.flags = (b is not None, res is not None, rowadd is not None, int(rows_per_b))
-        ctx.defer = _can_defer(w, b)
+        ctx.defer = _can_defer(w, b if (b is not None and ctx.needs_input_grad[2]) else None)  # a frozen bias has no gradient to defer
         return ops.linear(x, w, b, res=res, rowadd=rowadd, rows_per_b=rows_per_b)
 
     @staticmethod
@@ -57,7 +57,9 @@ class Linear(Function):
         x, w = ctx.saved_tensors
         has_b, has_res, has_row, rpb = ctx.flags
         dy = dy.contiguous()
-        dx, dw, db = bw.linear_backward(x, w, dy, need_bias=has_b, defer=ctx.defer)
+        # a frozen weight / bias (a LoRA step freezes almost all of them) costs no gradient work
+        need_dw, need_b = ctx.needs_input_grad[1], has_b and ctx.needs_input_grad[2]
+        dx, dw, db = bw.linear_backward(x, w, dy, need_bias=need_b, defer=ctx.defer and need_dw, need_dw=need_dw)
         drow = bw.colsum(dy, rows_per_group=rpb).to(dy.dtype) if has_row else None
         return dx, dw, db, (dy if has_res else None), drow, None
 
@@ -106,7 +108,7 @@ class Conv3x3(Function):
     def forward(ctx, x, wp, b, res, rowadd, stride):
         ctx.save_for_backward(x, wp)
         ctx.flags = (b is not None, res is not None, rowadd is not None, int(stride))
-        ctx.defer = _can_defer(wp, b)
+        ctx.defer = _can_defer(wp, b if (b is not None and ctx.needs_input_grad[2]) else None)
         return ops.conv3x3(x, wp, b, stride=stride, rowadd=rowadd, res=res)
 
     @staticmethod
@@ -114,8 +116,9 @@ class Conv3x3(Function):
         x, wp = ctx.saved_tensors
         has_b, has_res, has_row, stride = ctx.flags
         dy = dy.contiguous()
-        dx, dw, db = bw.conv3x3_backward(x, wp, dy, need_bias=has_b, stride=stride, need_dx=ctx.needs_input_grad[0],
-                                         defer=ctx.defer)
+        need_dw, need_b = ctx.needs_input_grad[1], has_b and ctx.needs_input_grad[2]
+        dx, dw, db = bw.conv3x3_backward(x, wp, dy, need_bias=need_b, stride=stride, need_dx=ctx.needs_input_grad[0],
+                                         defer=ctx.defer and need_dw, need_dw=need_dw)
         drow = None
         if has_row:
             drow = bw.colsum(bw._pad_cols64(dy), rows_per_group=dy.shape[1] * dy.shape[2])[:, : dy.shape[-1]].to(dy.dtype)
@@ -171,7 +174,7 @@ class GroupNorm(Function):
         x, gamma, beta = ctx.saved_tensors
         eps, groups, silu = ctx.cfg
         dx, dg, db = bw.groupnorm_backward(x, dy.contiguous(), gamma, beta, eps, groups=groups, silu=silu, stats=ctx.stats,
-                                            defer=ctx.defer)
+                                            defer=ctx.defer, need_params=ctx.needs_input_grad[1] or ctx.needs_input_grad[2])
         return dx, dg, db, None, None, None
 
 
@@ -185,7 +188,8 @@ class LayerNorm(Function):
     @staticmethod
     def backward(ctx, dy):
         x, gamma = ctx.saved_tensors
-        dx, dg, db = bw.layernorm_backward(x, dy.contiguous(), gamma, ctx.eps)
+        dx, dg, db = bw.layernorm_backward(x, dy.contiguous(), gamma, ctx.eps,
+                                           need_params=ctx.needs_input_grad[1] or ctx.needs_input_grad[2])
         return dx, dg, db, None
 
 
@@ -208,7 +212,8 @@ class LayerNormSkip(Function):
         if dy is None:
             return dskip, None, None, None
         skip = dskip.contiguous() if dskip is not None else None
-        dx, dg, db = bw.layernorm_backward(x, dy.contiguous(), gamma, ctx.eps, skip=skip, defer=ctx.defer)
+        dx, dg, db = bw.layernorm_backward(x, dy.contiguous(), gamma, ctx.eps, skip=skip, defer=ctx.defer,
+                                           need_params=ctx.needs_input_grad[1] or ctx.needs_input_grad[2])
         return dx, dg, db, None
 
 
@@ -385,6 +390,7 @@ class PackConvWeight(Function):
         else:
             check(lib.ur_unpack_conv_weight_grad(dwp.data_ptr(), dwp.stride(0), g.data_ptr(), co, ci, cp, DT[dwp.dtype], _stream()),
                   "ur_unpack_conv_weight_grad")
+        bw.wgrad_stats["matrices"] += 1
         return g, None, None
 
 
@@ -444,6 +450,7 @@ class PackConvWeights(Function):
                 check(lib.ur_unpack_conv_weight_grad(dwp.data_ptr(), dwp.stride(0), g.data_ptr(), co, ci, cp, DT[dwp.dtype], _stream()),
                       "ur_unpack_conv_weight_grad")
             res.append(g)
+        bw.wgrad_stats["matrices"] += sum(r is not None for r in res)
         return (None, None, *res)
 
 
@@ -498,6 +505,7 @@ class CastParams(Function):
             bw.weight_t.pop(key, None)
         idx = [i for i, g in enumerate(grads) if g is not None]
         res = [None] * len(grads)
+        bw.wgrad_stats["matrices"] += len(idx)
         if idx:
             # destinations: the parameters' slices of their communication buckets where a sink is installed (bw.GradSink)
             sink = None
@@ -513,3 +521,102 @@ class CastParams(Function):
             for i, o_ in zip(idx, outs):
                 res[i] = o_
         return (None, *res)
+
+
+_lora_tables: dict = {}  # addresses and sizes of a LoraMerge launch list -> its host item tables (eager steps repeat them)
+
+
+def _lora_cached(kind, rows, build):
+    """The host item tables of ``rows`` (tensors and floats), built once per distinct list of addresses: a table build costs
+    ~0.3 ms of host time per 160 matrices (profiles/lora_ab.txt), and an eager step repeats the same addresses."""
+    key = (kind,) + tuple((x.data_ptr(), tuple(x.shape)) if torch.is_tensor(x) else x for row in rows for x in row)
+    hit = _lora_tables.get(key)
+    if hit is None:
+        if len(_lora_tables) >= 16:
+            _lora_tables.clear()
+        hit = _lora_tables[key] = build()
+    return hit
+
+
+class LoraMerge(Function):
+    """The merged weights of a network with a TRAINABLE LoRA adapter as one autograd node per network forward, modelled on
+    CastParams: ``W'_i = src_i + scale * factor_i * up_i @ down_i`` for all adapted matrices, written into ONE packed
+    compute-dtype buffer by one grouped launch per 48 matrices (``ur_lora_merge_cast_multi``: ``src`` -- the untouched fp32 /
+    half ``base`` -- is read in its own dtype, one rounding).  The outputs register like CastParams outputs (deferred weight
+    gradients, W^T for the dx GEMMs).  The backward flushes the deferred weight-gradient queue and projects every ``dW'_i`` onto
+    its factors with one grouped launch per 48 matrices (``ur_lora_grad_multi``); the fp32 ``d_down`` / ``d_up`` go to autograd,
+    which accumulates them into ``.grad``.  Neither direction writes ``src`` or the parameters, reads the host, or keeps state
+    that a graph capture could not hold: the item tables carry addresses only.
+
+    ``apply(dtype, scale, meta, *factors)``: ``meta`` = [(src [N, K...], factor)] per matrix, ``factors`` = down_0, up_0, down_1,
+    up_1, ... (fp32, contiguous)."""
+
+    @staticmethod
+    def forward(ctx, dtype, scale, meta, *factors):
+        import weakref
+        from . import lora
+
+        ctx.set_materialize_grads(False)
+        srcs = [m[0] for m in meta]
+        dev = srcs[0].device
+        flat = torch.empty(sum(s.numel() for s in srcs), dtype=dtype, device=dev)
+        outs, off = [], 0
+        for s in srcs:
+            outs.append(flat[off: off + s.numel()].view(s.shape))
+            off += s.numel()
+        downs = [f.detach() for f in factors[0::2]]
+        ups = [f.detach() for f in factors[1::2]]
+        ctx.scales = [float(scale) * float(m[1]) for m in meta]
+        by_dtype: dict = {}
+        for s, o, d, u, sc in zip(srcs, outs, downs, ups, ctx.scales):
+            if not (s.is_contiguous() and d.is_contiguous() and u.is_contiguous() and d.dtype == u.dtype == torch.float32):
+                raise RuntimeError("LoraMerge: contiguous matrices and contiguous fp32 factors")
+            by_dtype.setdefault(s.dtype, []).append((s, o.view(o.shape[0], -1), u, d, None, sc))
+        for sdt, rows in by_dtype.items():
+            tables = _lora_cached("merge", rows, lambda rows=rows: lora.item_tables(rows, lora.multi_max()))
+            lora.launch_merge_cast(tables, sdt, dtype)
+        ctx.save_for_backward(*downs, *ups)
+        ctx.wt_keys = []
+        _deferred_w[flat.untyped_storage().data_ptr()] = weakref.ref(flat)
+        bw.weight_t.sweep()
+        if bw.BATCH_WT and bw.WGRAD:
+            w2 = [o.reshape(o.shape[0], -1) for o in outs]
+            w2 = [o for o in w2 if o.shape[0] % 8 == 0 and o.shape[1] % 8 == 0 and o.numel()]
+            for o, t in zip(w2, bw.transpose2d_many(w2) if w2 else []):
+                key = (o.data_ptr(), tuple(o.shape))
+                bw.weight_t.put(key, flat, t)  # valid while the flat buffer is alive
+                ctx.wt_keys.append(key)
+        return tuple(outs)
+
+    @staticmethod
+    def backward(ctx, *grads):
+        from . import lora
+
+        bw.wgrad_queue.flush()  # the weight gradients below may have been handed out uninitialised (Linear.backward)
+        for key in ctx.wt_keys:
+            bw.weight_t.pop(key, None)
+        saved = ctx.saved_tensors
+        n = len(saved) // 2
+        downs, ups = saved[:n], saved[n:]
+        res = [None] * (2 * n)
+        idx = [i for i, g in enumerate(grads) if g is not None]
+        bw.wgrad_stats["matrices"] += len(idx)
+        if idx:
+            # one fp32 buffer for all factor gradients of the node: d_down_i | d_up_i back to back
+            sizes = [downs[i].numel() + ups[i].numel() for i in idx]
+            flat = torch.empty(sum(sizes), dtype=torch.float32, device=downs[0].device)
+            by_dtype: dict = {}
+            off = 0
+            for i in idx:
+                g = grads[i].reshape(grads[i].shape[0], -1)
+                g = g if g.is_contiguous() else g.contiguous()
+                dd = flat[off: off + downs[i].numel()].view(downs[i].shape)
+                off += downs[i].numel()
+                du = flat[off: off + ups[i].numel()].view(ups[i].shape)
+                off += ups[i].numel()
+                res[2 * i], res[2 * i + 1] = dd, du
+                by_dtype.setdefault(g.dtype, []).append((g, ups[i], downs[i], None, du, dd, ctx.scales[i]))
+            for gdt, rows in by_dtype.items():
+                tables = _lora_cached("grad", rows, lambda rows=rows: lora.grad_item_tables(rows, lora.multi_max()))
+                lora.launch_grad(tables, gdt)
+        return (None, None, None, *res)

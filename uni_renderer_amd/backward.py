@@ -319,6 +319,11 @@ WGRAD_SPLITS = X.number("wgrad_splits", 0)
 WGRAD_TABLE_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "wgrad_tuning.json")
 _wgrad_table: Optional[dict] = None
 WGRAD_TRACE: Optional[dict] = None  # set to a dict to count the problems that pass through wgrad() (the tuner's input)
+# "problems": weight-gradient problems EXECUTED (one per dw GEMM, whichever path computed it) since a caller last zeroed the
+# counters: a frozen weight costs none (Linear / Conv3x3 backward pass autograd's needs_input_grad through), which is what a
+# LoRA step relies on.  "matrices": weight matrices that received a gradient from them at the nodes that own the compute-dtype
+# copies (CastParams, PackConvWeight(s), LoraMerge) -- q | k | v of a self-attention are one problem and three matrices.
+wgrad_stats = {"problems": 0, "matrices": 0}
 
 
 def wgrad_table() -> dict:
@@ -399,6 +404,7 @@ def wgrad(dy2: torch.Tensor, x: torch.Tensor, need_bias: bool = True, conv: Opti
         part = torch.empty(int(lib.ur_wgrad_partial_floats(C.byref(d))), dtype=torch.float32, device=dy2.device)
         d.partial = part.data_ptr()
     check(lib.ur_wgrad(C.byref(d), _stream()), "ur_wgrad")
+    wgrad_stats["problems"] += 1
     return dw, db
 
 
@@ -570,6 +576,7 @@ def wgrad_group(items, tile: int = 0, splits: int = 0, trace: Optional[dict] = N
         part = torch.empty(int(lib.ur_wgrad_partial_floats(C.byref(d))) * n, dtype=torch.float32, device=dy0.device)
         d.partial = part.data_ptr()
     check(lib.ur_wgrad_group(C.byref(d), g, n, _stream()), "ur_wgrad_group")
+    wgrad_stats["problems"] += n
 
 
 def _pad_rows64(t: torch.Tensor) -> torch.Tensor:
@@ -582,12 +589,17 @@ def _pad_rows64(t: torch.Tensor) -> torch.Tensor:
     return out
 
 
-def linear_backward(x: torch.Tensor, w: torch.Tensor, dy: torch.Tensor, need_bias: bool = True, defer: bool = False
-                    ) -> Tuple[torch.Tensor, torch.Tensor, Optional[torch.Tensor]]:
+def linear_backward(x: torch.Tensor, w: torch.Tensor, dy: torch.Tensor, need_bias: bool = True, defer: bool = False,
+                    need_dw: bool = True) -> Tuple[torch.Tensor, Optional[torch.Tensor], Optional[torch.Tensor]]:
     """y = x @ w^T + b  (x [..., K], w [N, K] in the compute dtype, dy [..., N])  ->  (dx, dw, db).
-    dx = dy @ w, dw = dy^T @ x (both through ``ur_igemm``), db = column sums of dy (fp32)."""
+    dx = dy @ w, dw = dy^T @ x (both through ``ur_igemm``), db = column sums of dy (fp32).  ``need_dw=False`` (a frozen
+    weight): no weight-gradient work, dw is None."""
     K, N = x.shape[-1], w.shape[0]
     x2, dy2 = x.reshape(-1, K), dy.reshape(-1, N)
+    if not need_dw:
+        wt = weight_t.lookup((w.data_ptr(), tuple(w.shape)))
+        dx = ops.linear(dy2, wt if wt is not None else transpose2d(w)).view(x.shape)
+        return dx, None, (colsum(dy2.contiguous()) if need_bias else None)
     if WGRAD and wgrad_ok(dy2, x2):
         wt = weight_t.lookup((w.data_ptr(), tuple(w.shape)))
         dx = ops.linear(dy2, wt if wt is not None else transpose2d(w)).view(x.shape)   # [M, N] @ [K, N]^T
@@ -602,6 +614,7 @@ def linear_backward(x: torch.Tensor, w: torch.Tensor, dy: torch.Tensor, need_bia
         (wt, dyt, xt), db = transpose2d_many([w, dy2p, x2], pad64=(1, 2)), None
     dx = ops.linear(dy2, wt).view(x.shape)                # [M, N] @ [K, N]^T
     dw = ops.linear(dyt, xt)                              # [N, M] @ [K, M]^T = [N, K]
+    wgrad_stats["problems"] += 1
     return dx, dw, db
 
 
@@ -666,12 +679,14 @@ def _pad_cols64(t: torch.Tensor) -> torch.Tensor:
 
 
 def conv3x3_backward(x: torch.Tensor, w_packed: torch.Tensor, dy: torch.Tensor, need_bias: bool = True, stride: int = 1,
-                     need_dx: bool = True, defer: bool = False) -> Tuple[Optional[torch.Tensor], torch.Tensor, Optional[torch.Tensor]]:
+                     need_dx: bool = True, defer: bool = False, need_dw: bool = True
+                     ) -> Tuple[Optional[torch.Tensor], Optional[torch.Tensor], Optional[torch.Tensor]]:
     """3x3 / pad 1 / stride 1|2 conv over NHWC x [B,H,W,C] (C % 64 == 0) with packed weights [N][(ky,kx,c)],
     dy [B,Ho,Wo,N]  ->  (dx [B,H,W,C], dw [N][(ky,kx,c)], db [N] fp32).
     dx is the same implicit-GEMM conv applied to dy (zero-inserted for stride 2) with the rotated / channel-transposed
     weights; dw contracts dy^T with the transposed im2col of x over the B*Ho*Wo output pixels.  N is zero-padded to a
-    multiple of 64 internally (conv_out has 4 / 28 channels)."""
+    multiple of 64 internally (conv_out has 4 / 28 channels).  ``need_dw=False`` (a frozen weight): no weight-gradient work,
+    dw is None."""
     lib = _lib.load()
     B, H, W, Cc = x.shape
     N = w_packed.shape[0]
@@ -689,6 +704,8 @@ def conv3x3_backward(x: torch.Tensor, w_packed: torch.Tensor, dy: torch.Tensor, 
         if dx.shape[1] != H or dx.shape[2] != W:
             raise RuntimeError("conv3x3_backward: odd input sizes are not supported with stride 2")
     P = B * Ho * Wo
+    if not need_dw:
+        return dx, None, (colsum(dyp.reshape(P, Np))[:N].contiguous() if need_bias else None)
     xc = x.contiguous()
     if WGRAD and wgrad_ok(dyp.reshape(P, Np), xc, (Ho, Wo)):
         later = None
@@ -709,6 +726,7 @@ def conv3x3_backward(x: torch.Tensor, w_packed: torch.Tensor, dy: torch.Tensor, 
         dyt, db = transpose2d(dyp.reshape(P, Np)), None
     dyt = _pad_rows64(dyt)                                    # [Np, Pp]
     dw = ops.linear(dyt, xcol_t)[:N]                          # [Np, Pp] @ [9C, Pp]^T = [Np, 9C]
+    wgrad_stats["problems"] += 1
     return dx, dw, db
 
 
@@ -746,9 +764,10 @@ GN_BWD_FUSED_MAX_ROWS = X.number("gn_bwd_fused_max_rows", 1024)
 
 
 def groupnorm_backward(x: torch.Tensor, dy: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: float,
-                       groups: int = 32, silu: bool = False, stats: Optional[torch.Tensor] = None, defer: bool = False
-                       ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
-    """x, dy NHWC [B,H,W,C]; y = act(GN(x)*gamma + beta).  -> (dx, dgamma, dbeta) (the last two fp32).
+                       groups: int = 32, silu: bool = False, stats: Optional[torch.Tensor] = None, defer: bool = False,
+                       need_params: bool = True) -> Tuple[torch.Tensor, Optional[torch.Tensor], Optional[torch.Tensor]]:
+    """x, dy NHWC [B,H,W,C]; y = act(GN(x)*gamma + beta).  -> (dx, dgamma, dbeta) (the last two fp32; None with
+    ``need_params=False``, frozen gamma / beta: their sums are not run).
     ``stats``: the forward pass's partial statistics when it kept them; otherwise they are recomputed with
     ``ur_groupnorm_stats`` (one more read of x)."""
     _require_gpu(x)
@@ -765,6 +784,8 @@ def groupnorm_backward(x: torch.Tensor, dy: torch.Tensor, gamma: torch.Tensor, b
         check(lib.ur_groupnorm_backward_fused(x.data_ptr(), dy.data_ptr(), Cc, B, rows, groups, gamma.data_ptr(), beta.data_ptr(),
                                               float(eps), int(silu), chan_sum.data_ptr(), dx.data_ptr(), DT[x.dtype], s),
               "ur_groupnorm_backward_fused")
+        if not need_params:
+            return dx, None, None
         if defer and NORM_DEFER and norm_sums.fresh(gamma):
             sums = norm_sums.add(chan_sum.view(B, 2 * Cc), True).view(2, Cc)
             return dx, sums[1], sums[0]
@@ -785,6 +806,8 @@ def groupnorm_backward(x: torch.Tensor, dy: torch.Tensor, gamma: torch.Tensor, b
     check(lib.ur_groupnorm_backward(x.data_ptr(), dy.data_ptr(), Cc, B, rows, groups, nstat, part.data_ptr(),
                                     gamma.data_ptr(), beta.data_ptr(), float(eps), int(silu), nred, chan_part.data_ptr(),
                                     chan_sum.data_ptr(), nchunks, dx.data_ptr(), DT[x.dtype], s), "ur_groupnorm_backward")
+    if not need_params:
+        return dx, None, None
     if defer and NORM_DEFER and norm_sums.fresh(gamma):
         sums = norm_sums.add(chan_sum.view(B, 2 * Cc), True).view(2, Cc)
         return dx, sums[1], sums[0]
@@ -794,9 +817,10 @@ def groupnorm_backward(x: torch.Tensor, dy: torch.Tensor, gamma: torch.Tensor, b
 
 
 def layernorm_backward(x: torch.Tensor, dy: torch.Tensor, gamma: torch.Tensor, eps: float = 1e-5,
-                       skip: Optional[torch.Tensor] = None, defer: bool = False) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
-    """x, dy [..., C] -> (dx, dgamma, dbeta) (fp32 parameter gradients).  ``skip``: a gradient reaching x around the norm
-    (same shape), added to dx by the kernel."""
+                       skip: Optional[torch.Tensor] = None, defer: bool = False, need_params: bool = True
+                       ) -> Tuple[torch.Tensor, Optional[torch.Tensor], Optional[torch.Tensor]]:
+    """x, dy [..., C] -> (dx, dgamma, dbeta) (fp32 parameter gradients; None with ``need_params=False``, frozen gamma / beta:
+    their sums are not run).  ``skip``: a gradient reaching x around the norm (same shape), added to dx by the kernel."""
     _require_gpu(x)
     lib = _lib.load()
     Cc = x.shape[-1]
@@ -808,6 +832,8 @@ def layernorm_backward(x: torch.Tensor, dy: torch.Tensor, gamma: torch.Tensor, e
     check(lib.ur_layernorm_backward_skip(x.data_ptr(), dy.data_ptr(), gamma.data_ptr(), float(eps), rows, Cc, rpw, dx.data_ptr(),
                                          part.data_ptr(), skip.data_ptr() if skip is not None else None, DT[x.dtype], _stream()),
           "ur_layernorm_backward_skip")
+    if not need_params:
+        return dx, None, None
     if defer and NORM_DEFER and norm_sums.fresh(gamma):
         sums = norm_sums.add(part.view(waves, 2 * Cc), False).view(2, Cc)
         return dx, sums[0], sums[1]

@@ -375,19 +375,17 @@ class UNet2DConditionModel(UNetLoraMixin, _DenoiserBase):
                          encoder_attention_mask=encoder_attention_mask)
         lora_scale = scale_of(cross_attention_kwargs)
         autograd = self._autograd_mode(sample, encoder_hidden_states, down_block_additional_residuals, mid_block_additional_residual)
-        if self._lora is not None:
-            if autograd:
-                from .train_step import LORA_AUTOGRAD_MSG
-
-                raise NotImplementedError(LORA_AUTOGRAD_MSG)
-            self._lora_apply(lora_scale)  # re-merges only when the wanted scale differs from the merged one
+        if self._lora is not None and not autograd:
+            self._lora_apply(lora_scale)  # re-merges only when the scale or a trainable factor differs from what was merged
         if autograd:
+            if self._lora is not None:
+                self._lora_train_plan(lora_scale)  # raises at once for an adapter set-up that cannot be trained
             return self._forward_autograd(sample, timestep, encoder_hidden_states, down_block_additional_residuals,
-                                          mid_block_additional_residual, return_dict)
+                                          mid_block_additional_residual, return_dict, lora_scale=lora_scale)
         state = self.forward_down_mid(sample, timestep, encoder_hidden_states)
         return self.forward_up(state, down_block_additional_residuals, mid_block_additional_residual, return_dict)
 
-    def _forward_autograd(self, sample, timestep, ehs, down_res, mid_res, return_dict):
+    def _forward_autograd(self, sample, timestep, ehs, down_res, mid_res, return_dict, lora_scale=None):
         """The differentiable forward (train_step.unet_forward) behind the reference's signature and return tuple."""
         from . import train_step as TS
 
@@ -400,7 +398,7 @@ class UNet2DConditionModel(UNetLoraMixin, _DenoiserBase):
         mid = TS.to_nhwc_grad(mid_res, dt) if mid_res is not None else None
         img, raw_down, raw_mid, ups = TS.unet_forward(self, TS.to_nhwc_grad(sample, dt, CIN_PAD),
                                                       TS._prompt(ehs, sample.shape[0], dt), timestep, dt, res, mid,
-                                                      collect_up=True)
+                                                      collect_up=True, lora_scale=lora_scale)
         v = lambda t: t.permute(0, 3, 1, 2)
         if not return_dict:
             return v(img), tuple(v(t) for t in raw_down), v(raw_mid), tuple(v(t) for t in ups)

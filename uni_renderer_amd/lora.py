@@ -18,6 +18,25 @@ Key formats of ``load_attn_procs`` (an optional leading ``unet.`` on all of them
   ``<attention>.processor.to_{q,k,v,out}_lora.{down,up}.weight``                    legacy attention processors
 where ``<module>`` is any ``Linear`` / ``Conv2d`` of the UNet under its ``state_dict`` name.  kohya ``lora_unet_*`` names,
 keys that match no module and factors whose shapes do not fit raise a ``ValueError`` naming the key.
+
+Training an adapter.  ``add_adapter`` (fresh factors: ``down`` ~ N(0, (1/rank)^2), ``up`` = 0) and
+``load_attn_procs(..., trainable=True)`` (resuming) register the fp32 factors as ``nn.Parameter``s under ONE container
+attribute of the UNet, ``lora_factors``: ``unet.parameters()`` yields them (optimizers, clipping, ``GradientBuckets`` and the
+graph signatures see them), ``state_dict()`` / ``load_state_dict()`` / ``save_pretrained()`` do not -- the network's checkpoint
+keeps its keys; ``save_attn_procs`` writes the file ``load_attn_procs`` reads.  The adapted weights are frozen by these calls.
+Under autograd the step still runs on merged weights: one autograd node per network forward (``autograd_ops.LoraMerge``)
+writes ``W' = base + s * (alpha / rank) * up @ down`` for all adapted matrices into one compute-dtype buffer with one grouped
+launch per 48 matrices (``ur_lora_merge_cast_multi``: fp32 ``base`` in, ONE rounding), the network runs forward and backward
+on ``W'`` exactly as on cast weights -- deferred, grouped ``ur_wgrad_group`` included -- and the node's backward projects the
+weight gradients ``dW'`` onto the factors, again one grouped launch per 48 matrices (``ur_lora_grad_multi``):
+``d_up = s (alpha / rank) dW' down^T``, ``d_down = s (alpha / rank) up^T dW'``.  The parameters and ``base`` are never written
+by the differentiable forward; the inference path re-merges when the scale OR any factor's ``(data_ptr, _version)`` differs
+from what the last merge read, so a ``no_grad`` forward after optimizer steps sees the updated factors.
+The alternative that was not built: projecting without ever forming ``dW'`` (``dy^T (x down^T)``) needs fewer FLOPs but four
+skinny GEMMs per layer and a grouped kernel family of its own.  Out of scope: trainable adapters on 3x3 convs (the
+differentiable path keeps those weights in the packed ``[N][(ky, kx, c)]`` layout, which is not the matrix the factors multiply),
+on the encoder / decoder networks and on the text encoder, kohya files, several trainable adapters at once, dropout in the LoRA
+branch, optimizer-state resume through ``checkpointing.py`` and multi-GPU runs.
 """
 from __future__ import annotations
 
@@ -33,6 +52,8 @@ from . import _lib
 
 LORA_WEIGHT_NAME = "pytorch_lora_weights.safetensors"
 ITEM_WORDS = 9  # int64_t words per item of ur_lora_merge_multi's table: base, w, up, down, rscale, N, K, R, scale bits
+GRAD_ITEM_WORDS = 10  # ... of ur_lora_grad_multi's: dw, up, down, rscale, d_up, d_down, N, K, R, scale bits
+FACTORS_ATTR = "lora_factors"  # the container attribute of a UNet with a trainable adapter
 _DT = {torch.float16: _lib.ABI.UR_DT_F16, torch.bfloat16: _lib.ABI.UR_DT_BF16, torch.float32: _lib.ABI.UR_DT_F32}
 
 _PATTERNS = (
@@ -126,6 +147,19 @@ def parse_adapter(model: nn.Module, state_dict: Dict[str, torch.Tensor], network
     return out
 
 
+def alpha_modules(state_dict, network_alphas=None) -> set:
+    """The module names an adapter file (``.alpha`` keys) or ``network_alphas`` give an alpha for."""
+    out = set()
+    for src in (network_alphas or {}), [k for k in state_dict if k.endswith(".alpha")]:
+        for k in src:
+            name = _strip(k)
+            name = name[:-len(".alpha")] if name.endswith(".alpha") else name
+            for suffix in (".lora", ".processor"):
+                name = name[:-len(suffix)] if name.endswith(suffix) else name
+            out.add(name)
+    return out
+
+
 def read_lora_file(path_or_dict, weight_name: Optional[str] = None) -> Dict[str, torch.Tensor]:
     """A state dict as given, a ``.safetensors`` file, or a directory holding ``weight_name``.  Local files only."""
     if isinstance(path_or_dict, dict):
@@ -140,11 +174,40 @@ def read_lora_file(path_or_dict, weight_name: Optional[str] = None) -> Dict[str,
     return load_file(path)
 
 
+class LoraFactors(nn.Module):
+    """The container of a trainable adapter's factors: ``nn.Parameter``s that ``parameters()`` of the model yields and its
+    ``state_dict()`` / ``load_state_dict()`` do not see.  ``names[i]`` is the module of the pair ``down_i`` / ``up_i``."""
+
+    def __init__(self):
+        super().__init__()
+        self.names: List[str] = []
+
+    def add(self, name: str, down: torch.Tensor, up: torch.Tensor):
+        i = len(self.names)
+        self.names.append(name)
+        self.register_parameter(f"down_{i}", nn.Parameter(down, requires_grad=True))
+        self.register_parameter(f"up_{i}", nn.Parameter(up, requires_grad=True))
+        return getattr(self, f"down_{i}"), getattr(self, f"up_{i}")
+
+    def state_dict(self, *args, destination=None, prefix="", keep_vars=False):
+        return destination if destination is not None else OrderedDict()
+
+    def _save_to_state_dict(self, destination, prefix, keep_vars):
+        return
+
+    def _load_from_state_dict(self, *args, **kwargs):
+        return
+
+
 class _LoraState:
     """What a model with adapters keeps: the adapters, the active ones with their weights, the ``base`` copies and the
     merged / pinned scale."""
 
     def __init__(self):
+        self.trainable: Optional[str] = None       # the adapter whose factors are Parameters (LoraFactors), if any
+        self.alphas: Dict[str, Dict[str, float]] = {}  # adapter -> {module: lora_alpha} where one was given (lora_state_dict)
+        self.thawed: List[str] = []                # modules whose weight required a gradient before the trainable adapter froze it
+        self.factor_sig: Optional[tuple] = None    # (data_ptr, _version) of every active factor as the last merge read them
         self.adapters: "OrderedDict[str, dict]" = OrderedDict()
         self.active: List[str] = []
         self.weights: Dict[str, float] = {}
@@ -185,6 +248,11 @@ class _LoraState:
                 out[name] = (torch.cat(ups, 1).contiguous(), torch.cat(downs, 0).contiguous(), torch.cat(rs).contiguous())
             self._assembled = out
         return self._assembled
+
+
+def factor_signature(st: _LoraState) -> tuple:
+    """``(data_ptr, _version)`` of every factor of the active adapters."""
+    return tuple((t.data_ptr(), t._version) for a in st.active for down, up, _ in st.adapters[a].values() for t in (down, up))
 
 
 def multi_max() -> int:
@@ -228,6 +296,57 @@ def merge_items(rows, dtype: torch.dtype) -> None:
         _lib.check(lib.ur_lora_merge_multi(table, k, _DT[dtype], _stream()), "ur_lora_merge_multi")
 
 
+def grad_item_tables(rows, nmax: int) -> list:
+    """The item tables of ``ur_lora_grad_multi`` over ``rows`` of (dw, up, down, rscale or None, d_up, d_down, scale): one
+    ctypes ``int64_t [k][10]`` array and its k per ``nmax`` rows."""
+    import ctypes
+    import struct
+
+    def words(row):
+        dw, up, down, rscale, d_up, d_down, scale = row
+        return (dw.data_ptr(), up.data_ptr(), down.data_ptr(), 0 if rscale is None else rscale.data_ptr(), d_up.data_ptr(),
+                d_down.data_ptr(), up.shape[0], down.shape[1], up.shape[1], struct.unpack("<I", struct.pack("<f", scale))[0])
+
+    tables = []
+    for i in range(0, len(rows), nmax):
+        part = rows[i:i + nmax]
+        tables.append(((ctypes.c_int64 * (GRAD_ITEM_WORDS * len(part)))(*(int(x) for row in part for x in words(row))), len(part)))
+    return tables
+
+
+def launch_merge_cast(tables, base_dtype: torch.dtype, out_dtype: torch.dtype) -> None:
+    """``ur_lora_merge_cast_multi`` over ready ``item_tables``."""
+    from .ops import _stream
+
+    lib = _lib.load()
+    for table, k in tables:
+        _lib.check(lib.ur_lora_merge_cast_multi(table, k, _DT[base_dtype], _DT[out_dtype], _stream()), "ur_lora_merge_cast_multi")
+
+
+def merge_cast_items(rows, base_dtype: torch.dtype, out_dtype: torch.dtype) -> None:
+    """``merge_items`` with ``base`` read in ``base_dtype`` and ``w`` written in ``out_dtype``."""
+    launch_merge_cast(item_tables(rows, multi_max()), base_dtype, out_dtype)
+
+
+def launch_grad(tables, dw_dtype: torch.dtype) -> None:
+    """``ur_lora_grad_multi`` over ready ``grad_item_tables``."""
+    from .ops import _stream
+
+    lib = _lib.load()
+    if lib.ur_lora_grad_item_words() != GRAD_ITEM_WORDS:
+        raise _lib.UrLibraryError(f"ur_lora_grad_multi takes {lib.ur_lora_grad_item_words()} words per item, this package writes {GRAD_ITEM_WORDS}")
+    for table, k in tables:
+        _lib.check(lib.ur_lora_grad_multi(table, k, _DT[dw_dtype], _stream()), "ur_lora_grad_multi")
+
+
+def grad_items(rows, dw_dtype: torch.dtype) -> None:
+    """One ``ur_lora_grad_multi`` launch per ``multi_max()`` rows (``grad_item_tables``) of one ``dw`` dtype."""
+    launch_grad(grad_item_tables(rows, multi_max()), dw_dtype)
+
+
+DEFAULT_TARGETS = ("to_q", "to_k", "to_v", "to_out.0")
+
+
 class UNetLoraMixin:
     """``load_attn_procs`` / ``fuse_lora`` / ``unfuse_lora`` / ``unload_lora`` / ``set_adapters`` / ``lora_scale`` of
     ``UNet2DConditionModel`` (the encoder / decoder networks have no loader, as in the reference)."""
@@ -240,20 +359,99 @@ class UNetLoraMixin:
         return None if self._lora is None else self._lora.merged_scale
 
     def load_attn_procs(self, pretrained_model_name_or_path_or_dict, weight_name: Optional[str] = None,
-                        network_alphas: Optional[Dict[str, float]] = None, adapter_name: str = "default", **ignored_hub_kwargs):
+                        network_alphas: Optional[Dict[str, float]] = None, adapter_name: str = "default",
+                        trainable: bool = False, **ignored_hub_kwargs):
         """Adds the adapter ``adapter_name`` (a state dict, a ``.safetensors`` file or a directory holding ``weight_name``;
         local files only) and makes it active beside those already loaded.  On the GPU the weights are merged at once at
-        the pinned scale, or at 1.0 -- what a ``forward`` without ``cross_attention_kwargs`` uses."""
+        the pinned scale, or at 1.0 -- what a ``forward`` without ``cross_attention_kwargs`` uses.
+        ``trainable=True`` (resuming a run): the loaded factors become parameters as those of ``add_adapter`` do."""
         sd = read_lora_file(pretrained_model_name_or_path_or_dict, weight_name)
         st = self._lora if self._lora is not None else _LoraState()
         if adapter_name in st.adapters:
             raise ValueError(f"adapter name {adapter_name!r} is already in use; unload_lora() first or pick another name")
-        st.adapters[adapter_name] = parse_adapter(self, sd, network_alphas)
+        parsed = parse_adapter(self, sd, network_alphas)
+        if trainable:
+            parsed = self._lora_register(st, adapter_name, parsed,
+                                         {n: f * parsed[n][0].shape[0] for n, (_, _, f) in parsed.items()
+                                          if n in alpha_modules(sd, network_alphas)})
+        st.adapters[adapter_name] = parsed
         st.active.append(adapter_name)
         st.weights[adapter_name] = 1.0
         st._assembled = None
         self._lora = st
         self._lora_remerge()
+
+    def add_adapter(self, rank: int = 4, lora_alpha: Optional[float] = None, target_modules=DEFAULT_TARGETS,
+                    adapter_name: str = "default", generator: Optional[torch.Generator] = None):
+        """A fresh TRAINABLE adapter (diffusers' PEFT-era name for what the 0.24 training script does with
+        ``LoRAAttnProcessor``s) on every ``nn.Linear`` / 1x1 ``nn.Conv2d`` whose name ends in one of ``target_modules``:
+        ``down`` [rank][K] ~ N(0, (1 / rank)^2), ``up`` [N][rank] = 0 (``LoRALinearLayer``'s init), both fp32 parameters on
+        the weight's device; the update is scaled by ``lora_alpha / rank`` (1 without ``lora_alpha``).  The adapter becomes
+        loaded and active like one from ``load_attn_procs``; the adapted weights are frozen.  A target that resolves to a
+        3x3 conv raises a ``ValueError`` naming the module (module docstring)."""
+        rank = int(rank)
+        if rank < 1 or rank > max_rank():
+            raise ValueError(f"rank {rank}: 1 .. {max_rank()}")
+        st = self._lora if self._lora is not None else _LoraState()
+        if adapter_name in st.adapters:
+            raise ValueError(f"adapter name {adapter_name!r} is already in use; unload_lora() first or pick another name")
+        if st.trainable is not None:
+            raise ValueError(f"adapter {st.trainable!r} is trainable already: several trainable adapters at once are not supported")
+        targets = [target_modules] if isinstance(target_modules, str) else list(target_modules)
+        parsed = OrderedDict()
+        for name, m in self.named_modules():
+            if name == FACTORS_ATTR or not any(name == t or name.endswith("." + t) for t in targets):
+                continue
+            if not isinstance(m, (nn.Linear, nn.Conv2d)):
+                continue
+            w = m.weight
+            if isinstance(m, nn.Conv2d) and tuple(m.kernel_size) != (1, 1):
+                raise ValueError(f"{name}: a trainable LoRA adapter on a {m.kernel_size[0]}x{m.kernel_size[1]} conv is not supported "
+                                 "(Linear and 1x1 Conv2d are)")
+            K = w[0].numel()
+            down = torch.empty(rank, K, dtype=torch.float32)
+            down.normal_(0.0, 1.0 / rank, generator=generator)
+            parsed[name] = (down.to(w.device).contiguous(), torch.zeros(w.shape[0], rank, dtype=torch.float32, device=w.device),
+                            1.0 if lora_alpha is None else float(lora_alpha) / rank)
+        if not parsed:
+            raise ValueError(f"target_modules {tuple(targets)} name no Linear / Conv2d of {type(self).__name__}")
+        alphas = {} if lora_alpha is None else {n: float(lora_alpha) for n in parsed}
+        st.adapters[adapter_name] = self._lora_register(st, adapter_name, parsed, alphas)
+        st.active.append(adapter_name)
+        st.weights[adapter_name] = 1.0
+        st._assembled = None
+        self._lora = st
+        self._lora_remerge()
+
+    def lora_parameters(self, adapter_name: Optional[str] = None) -> List[nn.Parameter]:
+        """The factor parameters of the trainable adapter (down, up per module, in module order)."""
+        st = self._lora_trainable(adapter_name)
+        return [p for down, up, _ in st.adapters[st.trainable].values() for p in (down, up)]
+
+    def lora_state_dict(self, adapter_name: Optional[str] = None) -> Dict[str, torch.Tensor]:
+        """``{<module>.lora.down.weight, <module>.lora.up.weight, <module>.alpha}`` of the trainable adapter (alpha only where
+        ``lora_alpha`` was given), conv factors 4-D as diffusers stores them: what ``load_attn_procs`` reads."""
+        st = self._lora_trainable(adapter_name)
+        out = OrderedDict()
+        for name, (down, up, _) in st.adapters[st.trainable].items():
+            conv = self.get_submodule(name).weight.dim() == 4
+            d, u = down.detach().clone(), up.detach().clone()
+            out[name + ".lora.down.weight"] = d.reshape(d.shape[0], -1, 1, 1) if conv else d
+            out[name + ".lora.up.weight"] = u.reshape(u.shape[0], -1, 1, 1) if conv else u
+            if name in st.alphas.get(st.trainable, {}):
+                out[name + ".alpha"] = torch.tensor(st.alphas[st.trainable][name], dtype=torch.float32)
+        return out
+
+    def save_attn_procs(self, save_directory, weight_name: Optional[str] = None, safe_serialization: bool = True,
+                        adapter_name: Optional[str] = None):
+        """Writes ``lora_state_dict()`` to ``save_directory / pytorch_lora_weights.safetensors`` (or ``weight_name``)."""
+        if not safe_serialization:
+            raise NotImplementedError("save_attn_procs writes safetensors files only")
+        from safetensors.torch import save_file
+
+        os.makedirs(save_directory, exist_ok=True)
+        sd = {k: v.contiguous().cpu() for k, v in self.lora_state_dict(adapter_name).items()}
+        save_file(sd, os.path.join(os.fspath(save_directory), weight_name or LORA_WEIGHT_NAME))
 
     def set_adapters(self, adapter_names, adapter_weights=None):
         """Which loaded adapters are active, and their weights (default 1.0 each)."""
@@ -300,8 +498,68 @@ class UNetLoraMixin:
                 by_dtype.setdefault(w.dtype, []).append((name, (base, w.detach(), None, None, None, 0.0)))
             self._lora_launch(by_dtype)
         self._lora = None
+        if FACTORS_ATTR in self._modules:
+            del self._modules[FACTORS_ATTR]
+        for name in st.thawed:
+            self.get_submodule(name).weight.requires_grad_(True)
 
     # ---- internals ------------------------------------------------------------------------------------
+    def _lora_register(self, st: _LoraState, adapter_name: str, parsed, alphas: Dict[str, float]):
+        """Makes the factors of ``parsed`` parameters of the container and freezes the adapted weights; returns ``parsed``
+        holding the parameters."""
+        if st.trainable is not None:
+            raise ValueError(f"adapter {st.trainable!r} is trainable already: several trainable adapters at once are not supported")
+        for name in parsed:
+            m = self.get_submodule(name)
+            if isinstance(m, nn.Conv2d) and tuple(m.kernel_size) != (1, 1):
+                raise ValueError(f"{name}: a trainable LoRA adapter on a {m.kernel_size[0]}x{m.kernel_size[1]} conv is not supported "
+                                 "(Linear and 1x1 Conv2d are)")
+        box = LoraFactors()
+        out = OrderedDict()
+        for name, (down, up, factor) in parsed.items():
+            d, u = box.add(name, down.contiguous(), up.contiguous())
+            out[name] = (d, u, factor)
+            w = self.get_submodule(name).weight
+            if w.requires_grad:
+                st.thawed.append(name)  # unload_lora() gives the flag back
+                w.requires_grad_(False)
+        self.add_module(FACTORS_ATTR, box)
+        st.trainable = adapter_name
+        st.alphas[adapter_name] = dict(alphas)
+        return out
+
+    def _lora_trainable(self, adapter_name: Optional[str] = None) -> _LoraState:
+        st = self._lora_required()
+        if st.trainable is None or (adapter_name is not None and adapter_name != st.trainable):
+            raise ValueError(f"adapter {adapter_name!r} is not trainable" if adapter_name is not None else
+                             "no trainable LoRA adapter (add_adapter / load_attn_procs(..., trainable=True))")
+        return st
+
+    def _lora_train_plan(self, scale: Optional[float]):
+        """What the differentiable forward needs (autograd_ops.LoraMerge): ``(rows, s)`` with rows of (weight parameter,
+        source matrix, down, up, alpha / rank x adapter weight) per adapted module -- the source is ``base`` once something was
+        merged into the parameter, else the parameter -- and ``s`` the scale in force.  Raises when the set-up cannot train."""
+        st = self._lora
+        if st.trainable is None:
+            from .train_step import LORA_AUTOGRAD_MSG
+
+            raise NotImplementedError(LORA_AUTOGRAD_MSG)
+        if st.active != [st.trainable]:
+            raise ValueError(f"training needs the trainable adapter {st.trainable!r} to be the only active one (active: "
+                             f"{st.active}); set_adapters({st.trainable!r}) first")
+        s = st.fused_scale if st.fused_scale is not None else (1.0 if scale is None else float(scale))
+        rows = []
+        for name, (down, up, factor) in st.adapters[st.trainable].items():
+            w = self.get_submodule(name).weight
+            if w.requires_grad:
+                raise ValueError(f"{name}.weight requires a gradient beside its trainable LoRA adapter: freeze it "
+                                 "(requires_grad_(False)); the factors carry its training")
+            if down.device != w.device or up.device != w.device:
+                raise RuntimeError(f"the LoRA factors of {name} are not on the weight's device")
+            src = st.base[name] if (st.merged_scale is not None and name in st.base) else w
+            rows.append((w, src.detach(), down, up, factor * st.weights[st.trainable]))
+        return rows, s
+
     def _lora_required(self) -> _LoraState:
         if self._lora is None:
             raise ValueError("no LoRA adapter is loaded")
@@ -314,7 +572,10 @@ class UNetLoraMixin:
         if st is None:
             return
         wanted = st.fused_scale if st.fused_scale is not None else (1.0 if scale is None else float(scale))
-        if st.merged_scale is None or wanted != st.merged_scale:
+        stale = st.trainable is not None and st.factor_sig != factor_signature(st)  # an optimizer step wrote the factors
+        if stale:
+            st._assembled = None
+        if st.merged_scale is None or wanted != st.merged_scale or stale:
             self._lora_merge(wanted)
 
     def _lora_remerge(self) -> None:
@@ -357,6 +618,7 @@ class UNetLoraMixin:
                 by_dtype.setdefault(w.dtype, []).append((name, (st.base[name], w.detach(), up, down, rscale, float(scale))))
         self._lora_launch(by_dtype)
         st.merged_scale = float(scale)
+        st.factor_sig = factor_signature(st)
 
     def _lora_launch(self, by_dtype) -> None:
         """``by_dtype``: dtype -> [(module name, merge_items row)]."""

@@ -120,6 +120,7 @@ class FusedAdamW(torch.optim.Optimizer):
                 step_t = cached[3]
                 step_t += 1
                 self._launch(lib, group, cached[2], step_t, grad_scale, found_inf)
+                torch.autograd.graph.increment_version(ps)
                 continue
             for p in ps:
                 if p.dtype != torch.float32 or p.grad.dtype != torch.float32 or not p.is_cuda:
@@ -142,6 +143,10 @@ class FusedAdamW(torch.optim.Optimizer):
             # the cache holds raw addresses: keep what they point into alive next to it (states live in self.state)
             group["_ur_launches"] = (gptrs, tuple(p.data_ptr() for p in ps), arrays, step_t)
             self._launch(lib, group, arrays, step_t, grad_scale, found_inf)
+            # the kernel wrote the parameters through their addresses: bump their version counters, as an in-place torch op
+            # would, so that everything keyed by (data_ptr, _version) -- packed copies, captured inference graphs, a merged
+            # LoRA adapter's factor signature -- notices the update
+            torch.autograd.graph.increment_version(ps)
         return loss
 
     @staticmethod
@@ -379,6 +384,7 @@ class AdamW8bit(FusedAdamW):
                       "ur_adamw8_multi")
             # the fp32 tensors, and the step counter's correction after a skipped step, exactly as FusedAdamW
             self._launch(lib, group, cached[2], step_t, grad_scale, found_inf)
+            torch.autograd.graph.increment_version(ps)  # as FusedAdamW.step
         return loss
 
     def dequantized_state_dict(self):

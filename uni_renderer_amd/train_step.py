@@ -30,6 +30,7 @@ from .unet_2d_blocks import freeu_enabled
 BATCH_CASTS = X.flag("batch_casts", True)
 _cast: Dict[int, torch.Tensor] = {}          # id(fp32 weight) -> its compute-dtype copy, valid inside one network forward
 _castable: Dict[int, tuple] = {}             # id(network) -> (network, its Linear / 1x1-conv weights)
+_lora_merged: Dict[int, torch.Tensor] = {}   # id(adapted weight) -> its merged W' (autograd_ops.LoraMerge), same lifetime
 
 
 class _batched_casts:
@@ -37,10 +38,29 @@ class _batched_casts:
     the duration of a network forward; ``_wc`` / ``_w2`` pick the copies up.  Their gradients return to fp32 in one
     launch when the network's backward has produced the last of them."""
 
-    def __init__(self, net, dt):
-        self.net, self.dt = net, dt
+    def __init__(self, net, dt, lora=None):
+        self.net, self.dt, self.lora = net, dt, lora
+
+    def _merge_lora(self):
+        """The adapted weights of a network with a trainable LoRA adapter: ONE node (autograd_ops.LoraMerge) writes the merged
+        matrices W' in the compute dtype; ``_wc`` / ``_w2`` pick them up like cast copies.  Order = memory order of the packed
+        buffer: to_k / to_v of the cross-attentions first, then module order, as for the casts below, so q | k | v and k | v stay
+        neighbours when all of them are adapted (A.cat_adjacent)."""
+        rows, s = self.lora
+        first = {id(w): i for i, w in enumerate(w for m in self.net.modules() if isinstance(m, BasicTransformerBlock)
+                                                and getattr(m, "attn2", None) is not None
+                                                for w in (m.attn2.to_k.weight, m.attn2.to_v.weight))}
+        order = sorted(range(len(rows)), key=lambda i: (0, first[id(rows[i][0])]) if id(rows[i][0]) in first else (1, i))
+        rows = [rows[i] for i in order]
+        outs = A.LoraMerge.apply(self.dt, s, [(r[1], r[4]) for r in rows], *[f for r in rows for f in (r[2], r[3])])
+        for r, o in zip(rows, outs):
+            _cast[id(r[0])] = o
+            _lora_merged[id(r[0])] = o
+        self.lkeys = [id(r[0]) for r in rows]
 
     def __enter__(self):
+        if self.lora is not None and torch.is_grad_enabled():
+            self._merge_lora()
         if not (BATCH_CASTS and torch.is_grad_enabled()):
             return self
         hit = _castable.get(id(self.net))
@@ -90,6 +110,9 @@ class _batched_casts:
     def __exit__(self, *exc):
         for k in getattr(self, "keys", ()):
             _cast.pop(k, None)
+        for k in getattr(self, "lkeys", ()):
+            _cast.pop(k, None)
+            _lora_merged.pop(k, None)
         for k in getattr(self, "bkeys", ()):
             A.deferred_bias.pop(k, None)
         for k in getattr(self, "ckeys", ()):
@@ -127,15 +150,15 @@ def _resnets_of(blocks, mid=None):
     return rs + (list(mid.resnets) if mid is not None else [])
 
 
-def _resnet(r, x, temb, dt, x1=None):
+def _resnet(r, x, temb, dt, x1=None, scw=None):
     """models/unet_2d_blocks.py:1100-1111 (ResnetBlock2D, time_embedding_norm='default'); ``temb``: the dict of
-    _temb_projections."""
+    _temb_projections; ``scw``: the [N, K] shortcut weight when the caller holds it (a LoRA-merged one under checkpointing)."""
     xin = torch.cat([x, x1], -1) if x1 is not None else x
     h = A.group_norm(xin, r.norm1.weight, r.norm1.bias, r.eps, r.groups, True)
     t = temb[id(r)]
     h = A.conv3x3(h, A.pack_conv_weight(r.conv1.weight, dt), r.conv1.bias, rowadd=t)
     h = A.group_norm(h, r.norm2.weight, r.norm2.bias, r.eps, r.groups, True)
-    sc = xin if r.conv_shortcut is None else A.linear(xin, _w2(r.conv_shortcut, dt), r.conv_shortcut.bias)
+    sc = xin if r.conv_shortcut is None else A.linear(xin, scw if scw is not None else _w2(r.conv_shortcut, dt), r.conv_shortcut.bias)
     if r.output_scale_factor != 1.0:
         raise NotImplementedError("output_scale_factor != 1 in the training path")
     return A.conv3x3(h, A.pack_conv_weight(r.conv2.weight, dt), r.conv2.bias, res=sc)
@@ -149,6 +172,14 @@ def _resnet_ckpt(blk, r, x, temb, dt, x1=None):
         from torch.utils.checkpoint import checkpoint
 
         t = temb[id(r)]
+        if r.conv_shortcut is not None and id(r.conv_shortcut.weight) in _lora_merged:
+            # a LoRA-merged shortcut weight exists only while its network forward runs: the recompute (in the backward) must be
+            # handed the very tensor, not look it up again
+            scw = _w2(r.conv_shortcut, dt)
+            fn = (lambda x_, t_, w_, x1_: _resnet(r, x_, {id(r): t_}, dt, x1=x1_, scw=w_)) if x1 is not None else \
+                 (lambda x_, t_, w_: _resnet(r, x_, {id(r): t_}, dt, scw=w_))
+            args = (x, t, scw, x1) if x1 is not None else (x, t, scw)
+            return checkpoint(fn, *args, use_reentrant=False)
         fn = (lambda x_, t_, x1_: _resnet(r, x_, {id(r): t_}, dt, x1=x1_)) if x1 is not None else \
              (lambda x_, t_: _resnet(r, x_, {id(r): t_}, dt))
         args = (x, t, x1) if x1 is not None else (x, t)
@@ -244,8 +275,9 @@ def _down_mid(net, x, temb_act, ehs, dt):
 FREEU_AUTOGRAD_MSG = ("FreeU is enabled on this network's up blocks, but the differentiable path has no backward for it: FreeU is a "
                       "sampling-time switch -- call disable_freeu() for training, or run the forward under torch.no_grad()")
 
-LORA_AUTOGRAD_MSG = ("a LoRA adapter is loaded on this network, but the differentiable path does not train adapters (they are merged "
-                     "into the weights): call unload_lora() for training, or run the forward under torch.no_grad()")
+LORA_AUTOGRAD_MSG = ("a LoRA adapter is loaded on this network that is not trainable (it is merged into the weights): train one made "
+                     "with add_adapter() or loaded with load_attn_procs(..., trainable=True), call unload_lora() to train the "
+                     "network itself, or run the forward under torch.no_grad()")
 
 
 def _up_out(net, x, skips: List[torch.Tensor], temb_act, ehs, dt, extras=None, collect=None):
@@ -315,13 +347,18 @@ def encoder_forward(enc, cond_nhwc, ehs, t_attr, dt, conditioning_scale: float =
     return res, mid_res, raw_enc, raw_mid_enc
 
 
-def unet_forward(unet, x_nhwc, ehs, t_img, dt, res=None, mid_res=None, collect_up: bool = False):
+def unet_forward(unet, x_nhwc, ehs, t_img, dt, res=None, mid_res=None, collect_up: bool = False, lora_scale=None):
     """UNet2DConditionModel (controlnet.py:781-1166).  ``x_nhwc`` [B,H,W,CIN_PAD]; ``res`` / ``mid_res``: the encoder's
-    residuals (NHWC) or None.  Returns (img_pred, raw_down[12], raw_mid, up_res[13] | None), NHWC."""
+    residuals (NHWC) or None.  Returns (img_pred, raw_down[12], raw_mid, up_res[13] | None), NHWC.
+    ``lora_scale``: the scale of a trainable LoRA adapter (``cross_attention_kwargs["scale"]``; None: 1.0, or the pinned one)."""
+    plan = None
     if getattr(unet, "_lora", None) is not None:
-        raise NotImplementedError(LORA_AUTOGRAD_MSG)
+        if torch.is_grad_enabled():
+            plan = unet._lora_train_plan(lora_scale)  # raises for an adapter that cannot be trained
+        else:
+            unet._lora_apply(lora_scale)  # the parameters hold the merged weights, as on the inference path
     B, dev = x_nhwc.shape[0], x_nhwc.device
-    with _batched_casts(unet, dt):
+    with _batched_casts(unet, dt, lora=plan):
         tu = _time(unet, t_img, B, dt, dev)
         xu = _conv(unet.conv_in, x_nhwc, dt, cin_pad=CIN_PAD)
         raw_mid_unet, raw_unet = _down_mid(unet, xu, tu, ehs, dt)
@@ -348,10 +385,13 @@ def decoder_forward(dec, raw_mid_enc, raw_enc, ehs, t_attr, dt, raw_unet=None, r
 
 
 def dual_stream_forward(unet, enc, dec, x_t, cond, ehs, t_img, t_attr, dtype=torch.bfloat16, run_decoder: bool = True,
-                        cond_nhwc: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+                        cond_nhwc: Optional[torch.Tensor] = None, cross_attention_kwargs=None) -> Dict[str, torch.Tensor]:
     """Differentiable dual-stream step (the call pattern of train.py:1324-1354): NCHW inputs, NHWC predictions
     ``img_pred`` [B,H,W,4] / ``attr_pred`` [B,H,W,28] in the compute dtype.  ``cond_nhwc`` ([B,H,W,28], compute dtype,
-    may require grad) replaces ``cond``: the cycle-consistency pass feeds the decoder's own prediction back in."""
+    may require grad) replaces ``cond``: the cycle-consistency pass feeds the decoder's own prediction back in.
+    ``cross_attention_kwargs``: ``{"scale": s}``, the scale of the UNet's trainable LoRA adapter (lora.py)."""
+    from .lora import scale_of
+
     B = x_t.shape[0]
     dt = dtype
     ehs = _prompt(ehs, B, dt)
@@ -360,7 +400,8 @@ def dual_stream_forward(unet, enc, dec, x_t, cond, ehs, t_img, t_attr, dtype=tor
     else:
         cin = ops.to_nhwc(cond, dt, CIN_PAD)
     res, mid_res, raw_enc, raw_mid_enc = encoder_forward(enc, cin, ehs, t_attr, dt)
-    img, raw_unet, raw_mid_unet, _ = unet_forward(unet, ops.to_nhwc(x_t, dt, CIN_PAD), ehs, t_img, dt, res, mid_res)
+    img, raw_unet, raw_mid_unet, _ = unet_forward(unet, ops.to_nhwc(x_t, dt, CIN_PAD), ehs, t_img, dt, res, mid_res,
+                                                  lora_scale=scale_of(cross_attention_kwargs))
     out = {"img_pred": img}
     if run_decoder:
         out["attr_pred"] = decoder_forward(dec, raw_mid_enc, raw_enc, ehs, t_attr, dt, raw_unet, raw_mid_unet)
@@ -635,6 +676,7 @@ class GraphedTrainStep:
         torch.cuda.synchronize()
         self.max_grad_norm = max_grad_norm
         self._kw = kw
+        self._updated = [p for grp in optimizer.param_groups for p in grp["params"] if p.requires_grad]
         self._capture()
 
     def _hyper(self):
@@ -734,6 +776,9 @@ class GraphedTrainStep:
                 torch.cuda.current_stream().synchronize()
             self.buckets.finish()
             self.g_up.replay()  # clipping (torch._foreach_norm over the buckets) + optimizer step
+        # a replay runs no Python: bump the version counters of what the captured update wrote, as the eager optimizer step does,
+        # so that packed copies, inference graphs and a merged LoRA adapter notice the new values
+        torch.autograd.graph.increment_version(self._updated)
         return self.stats
 
     def phase_times(self) -> Dict[str, float]:
