@@ -400,6 +400,50 @@ int ur_cond_conv3x3(const void* x, int x_dtype, int x_nchw, const void* w, const
 /* Host only: the k chunk CC (8, 16 or 32) of the weight image above, or UR_E_UNSUPPORTED for a stride / Cin the kernel refuses. */
 int ur_cond_conv3x3_kchunk(int Cin, int stride, int x_nchw);
 
+/*
+ * Backward of ur_cond_conv3x3 (csrc/condconv_bwd.hip; an ADDITION to ABI 17, nothing existing changes).  H, W, Cin, Cout and
+ * stride are the FORWARD's: x is [B][H][W][Cin], dy is [B][Ho][Wo][Cout] with Ho = (H - 1) / stride + 1, Wo likewise (odd H / W
+ * with stride 2 included).  Cout a multiple of 16, at most 256; Cin likewise except in image mode.
+ *
+ * Input gradient:
+ *   dx[b][y][x][c] = sum over (ky, kx, n) and the output pixels (oy, ox) with oy * stride - 1 + ky == y and ox * stride - 1 + kx == x
+ *                    of dy[b][oy][ox][n] * W[n][c][ky][kx]
+ *   dy, dx  NHWC in `dtype`; fp32 accumulation in a fixed order, ONE rounding to `dtype`.  Out-of-range taps contribute nothing,
+ *           a halo never reads the neighbouring sample, offsets are 64-bit.  A stride-2 layer's zero-inserted dy exists only in
+ *           the kernel's LDS staging rectangle: dy is read from memory once per pass of 96 input channels, never a padded copy.
+ *   w_rot   the rotated, channel-transposed weights in `dtype`, packed like the forward's image of a stride-1 layer with the
+ *           channel roles swapped: with CC = ur_cond_conv3x3_kchunk(Cout, 1, 0) (16 or 32 dy channels) and STEPS = ceil(9 * CC / 32)
+ *           the image is [Cin / 16][Cout / CC][STEPS][64][8]: element j of lane l of step s of chunk q of block cb is
+ *           W[q * CC + k % CC][cb * 16 + l % 16][2 - tap / 3][2 - tap % 3] with k = 32 * s + 8 * (l / 16) + j and tap = k / CC, and
+ *           zero where tap >= 9.
+ * The image-mode first layer has no input gradient.  Null pointers, sizes <= 0, an unknown dtype, dy / w_rot / dx not 16-byte
+ * aligned: UR_E_BADARG.  Any other stride, Cin or Cout: UR_E_UNSUPPORTED.  Both before any launch.
+ */
+int ur_cond_conv3x3_dgrad(const void* dy, const void* w_rot, void* dx, int B, int H, int W, int Cin, int Cout, int stride, int dtype,
+                          void* stream);
+
+/*
+ * Weight and bias gradient:
+ *   dw[n][c][ky][kx] = sum over (b, oy, ox) of dy[b][oy][ox][n] * x[b][oy * stride - 1 + ky][ox * stride - 1 + kx][c]     db[n] = sum of dy[...][n]
+ *   x       as ur_cond_conv3x3's: NHWC in `dtype`, or with x_nchw == 1 the caller's NCHW image [B][Cin][H][W], Cin = 1 .. 4, in
+ *           x_dtype = UR_DT_F16 / BF16 / F32, every element rounded to `dtype` first (as the forward does).
+ *   dw, db  fp32 in the parameter's own layout, [Cout][Cin][3][3] and [Cout] (image mode: the real channels only), OVERWRITTEN.
+ *           Either may be NULL, not both.
+ *   splits  the output pixels (in units of 4 rows x 32 columns of one sample) are split over `splits` workgroups per 32 x 32
+ *           channel tile; each writes an fp32 partial into `workspace`, a second launch adds the partials in a fixed order.  0: the
+ *           kernel's own choice (a function of the sizes only); > 0 (at most 65536): that count.  No atomics: a launch is
+ *           bit-reproducible for a given `splits`.
+ *   workspace, workspace_bytes   device memory of at least ur_cond_conv3x3_wgrad_workspace(same sizes, same splits) bytes,
+ *           16-byte aligned; its contents before and after the call are unspecified.
+ * Null x / dy / workspace, dw and db both null, sizes <= 0, splits < 0, an unknown dtype, a misaligned pointer, a workspace that
+ * is too small: UR_E_BADARG.  Any other stride, Cin, Cout or a splits above 65536: UR_E_UNSUPPORTED.  Both before any launch.
+ */
+int ur_cond_conv3x3_wgrad(const void* x, int x_dtype, int x_nchw, const void* dy, float* dw, float* db, void* workspace,
+                          int64_t workspace_bytes, int B, int H, int W, int Cin, int Cout, int stride, int splits, int dtype,
+                          void* stream);
+/* Host only: the workspace bytes of the call above, or (negative) the code with which it would refuse the sizes. */
+int64_t ur_cond_conv3x3_wgrad_workspace(int B, int H, int W, int Cin, int Cout, int stride, int x_nchw, int splits);
+
 /* ur_add_hilo (alpha = 1) over up to UR_ADD_MULTI_MAX independent tensor triples in ONE launch (ABI 10).  What a sampling
  * loop with a loop-invariant exchange operand runs per step instead of 13 exchange GEMMs: in the inverse-rendering loop
  * (models/pipeline.py:2629-2690) the UNet's skips are constant, so `control_down_blocks[i](skip_unet[i])`

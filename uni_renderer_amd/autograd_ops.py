@@ -125,6 +125,35 @@ class Conv3x3(Function):
         return dx, dw, db, (dy if has_res else None), drow, None
 
 
+class CondConv3x3(Function):
+    """A narrow 3x3 / pad 1 / stride 1 | 2 conv of the ControlNet conditioning embedding, WITHOUT activation (SiLU stays
+    ``SiLU``): ``x`` NHWC in the compute dtype, or with ``image`` the caller's NCHW image.  Takes the fp32 PARAMETERS
+    themselves (``weight`` [N, C, 3, 3], ``bias`` [N]) with their packed images ``wp`` / ``bp`` (packs.cond_conv3x3) and, where
+    dx is wanted, ``w_rot`` (packs.cond_conv3x3_rot): the weight gradient comes back in the parameter's shape and dtype, for a
+    ``bgr`` first layer flipped along the channel axis (the kernel reads the image as it lies in memory)."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, wp, bp, w_rot, stride, image, bgr, dtype):
+        ctx.save_for_backward(x, w_rot)
+        ctx.flags = (int(stride), bool(image), bool(bgr), weight.dtype, bias.dtype)
+        return ops.cond_conv3x3(x, wp, bp, n_out=weight.shape[0], stride=stride, act=ops.ACT_NONE, dtype=dtype, image=image)
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, w_rot = ctx.saved_tensors
+        stride, image, bgr, wdt, bdt = ctx.flags
+        need_dx, need_dw, need_b = ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.needs_input_grad[2]
+        dx, dw, db = bw.cond_conv3x3_backward(x, w_rot, dy, stride=stride, image=image, need_dx=need_dx, need_dw=need_dw,
+                                              need_bias=need_b)
+        if dw is not None:
+            if bgr:
+                dw = dw.flip(1)
+            dw = dw.to(wdt)
+        if db is not None:
+            db = db.to(bdt)
+        return dx, dw, db, None, None, None, None, None, None, None
+
+
 class Up2x(Function):
     """nearest 2x upsample (F.interpolate of Upsample2D, unet_2d_blocks.py:2501); backward = 2x2 sum pooling."""
 

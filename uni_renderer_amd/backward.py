@@ -730,6 +730,27 @@ def conv3x3_backward(x: torch.Tensor, w_packed: torch.Tensor, dy: torch.Tensor, 
     return dx, dw, db
 
 
+def cond_conv3x3_backward(x: torch.Tensor, w_rot: Optional[torch.Tensor], dy: torch.Tensor, stride: int = 1, image: bool = False,
+                          need_dx: bool = True, need_dw: bool = True, need_bias: bool = True, splits: int = 0
+                          ) -> Tuple[Optional[torch.Tensor], Optional[torch.Tensor], Optional[torch.Tensor]]:
+    """Backward of ``ops.cond_conv3x3`` (no activation) on the direct narrow-channel kernels (csrc/condconv_bwd.hip): ``x`` as the
+    forward read it (NHWC, or the NCHW image with ``image``), ``w_rot`` the ``layers.pack_cond_conv3x3_rot`` image (only read for
+    dx), dy [B,Ho,Wo,N]  ->  (dx [B,H,W,C] | None, dw [N,C,3,3] fp32 | None, db [N] fp32 | None).  The image layer has no dx.
+    One weight-gradient problem (``wgrad_stats``) per call that wants dw."""
+    dx = dw = db = None
+    dy = dy.contiguous()
+    if need_dx:
+        if image:
+            raise RuntimeError("cond_conv3x3_backward: the image-mode first layer has no input gradient")
+        dx = ops.cond_conv3x3_dgrad(dy, w_rot, in_hw=x.shape[1:3], n_in=x.shape[-1], stride=stride)
+    if need_dw or need_bias:
+        dw, db = ops.cond_conv3x3_wgrad(x, dy, stride=stride, image=image, need_dw=need_dw, need_bias=need_bias, splits=splits)
+        if need_dw:  # a frozen weight with a trainable bias costs the column sums only, as in conv3x3_backward
+            wgrad_stats["problems"] += 1
+            wgrad_stats["matrices"] += 1
+    return dx, dw, db
+
+
 def silu_backward(x: torch.Tensor, dy: torch.Tensor) -> torch.Tensor:
     lib = _lib.load()
     dx = torch.empty_like(x)

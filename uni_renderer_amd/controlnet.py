@@ -759,7 +759,9 @@ class ControlNetModel(_DenoiserBase):
     """Control of the UNet by an image (ref 2530-3266): the trunk of ``AttributeEncoderModel`` fed by
     ``conv_in(sample) + controlnet_cond_embedding(controlnet_cond)``.  ``forward(..., return_dict=False)`` returns
     ``(down_block_res_samples list[12], mid_block_res_sample)`` (ref 3260-3261), which go into
-    ``UNet2DConditionModel.forward`` as ``down_block_additional_residuals`` / ``mid_block_additional_residual``."""
+    ``UNet2DConditionModel.forward`` as ``down_block_additional_residuals`` / ``mid_block_additional_residual``.
+    With autograd recording and GPU tensors the forward is differentiable in every parameter (train_step.controlnet_forward);
+    CPU tensors raise ``CONTROLNET_AUTOGRAD_MSG``, an image that requires a gradient raises ``layers.COND_IMAGE_GRAD_MSG``."""
 
     @register_to_config
     def __init__(
@@ -870,7 +872,26 @@ class ControlNetModel(_DenoiserBase):
                          added_cond_kwargs=added_cond_kwargs)
         scale_of(cross_attention_kwargs)  # a LoRA scale is accepted and ignored: this network has no adapters
         if self._autograd_mode(sample, controlnet_cond, encoder_hidden_states):
-            raise NotImplementedError(CONTROLNET_AUTOGRAD_MSG)
+            # training (train_step.controlnet_forward: HIP forward AND backward kernels).  There is no differentiable path off
+            # the GPU, and none into the image.  Not covered: GraphedTrainStep, parallel.GradientBuckets / GradSink and LoRA
+            # for this network.
+            if not (sample.is_cuda and controlnet_cond.is_cuda and next(self.parameters()).is_cuda):
+                raise NotImplementedError(CONTROLNET_AUTOGRAD_MSG)
+            if controlnet_cond.requires_grad:
+                from .layers import COND_IMAGE_GRAD_MSG
+                raise NotImplementedError(COND_IMAGE_GRAD_MSG)
+            from . import train_step as TS
+
+            dt = _compute_dtype(self.dtype, self.compute_dtype)
+            res, mid = TS.controlnet_forward(
+                self, TS.to_nhwc_grad(sample, dt, CIN_PAD), controlnet_cond, TS._prompt(encoder_hidden_states, sample.shape[0], dt),
+                timestep, dt, conditioning_scale=float(conditioning_scale),
+                guess_mode=bool(guess_mode) and not self.config["global_pool_conditions"])
+            v = lambda t: t.permute(0, 3, 1, 2)
+            res, mid = [v(t) for t in res], v(mid)
+            if not return_dict:
+                return res, mid
+            return ControlNetOutput(down_block_res_samples=res, mid_block_res_sample=mid)
         B, _, H, W = sample.shape
         ctx = self._begin(B, timestep, sample.device, encoder_hidden_states)
         dt = ctx.dtype

@@ -106,6 +106,15 @@ def pack_cond_conv3x3(weight: torch.Tensor, dtype, stride: int = 1, image: bool 
     return w.to(dtype).contiguous()
 
 
+def pack_cond_conv3x3_rot(weight: torch.Tensor, dtype) -> torch.Tensor:
+    """[Co, Ci, 3, 3] -> the ``w_rot`` image ``ops.cond_conv3x3_dgrad`` reads (include/ur_kernels.h, ur_cond_conv3x3_dgrad): the
+    rotated, channel-transposed weights W_rot[c][n][ky][kx] = W[n][c][2 - ky][2 - kx] in the forward's image of a stride-1
+    layer with Co input and Ci output channels."""
+    if weight.shape[0] % 16 or weight.shape[1] % 16:
+        raise ValueError("pack_cond_conv3x3_rot: channels are multiples of 16 (the image-mode layer has no input gradient)")
+    return pack_cond_conv3x3(weight.detach().flip(2, 3).transpose(0, 1), dtype, 1)
+
+
 from . import packs as R  # noqa: E402 -- the recipes build on the primitives above
 from .packs import PackCache, one  # noqa: E402,F401 -- PackCache is imported from here by its other users
 
@@ -384,3 +393,28 @@ class ControlNetConditioningEmbedding(nn.Module):
             w, b = one(self._pk, R.cond_conv3x3(img, bgr), conv, dtype)
             x = ops.cond_conv3x3(x, w, b, n_out=conv.out_channels, stride=s, act=ops.ACT_SILU, dtype=dtype, image=img)
         return x
+
+    def forward_autograd(self, cond_nchw: torch.Tensor, dtype, bgr: bool = False) -> torch.Tensor:
+        """The same map under autograd: seven ``autograd_ops.CondConv3x3`` (forward kernel without activation; backward on the
+        direct narrow-channel dgrad / wgrad kernels) with ``autograd_ops.SiLU`` between them -- SiLU and its derivative are
+        elementwise passes of their own here, not conv epilogues.  The parameters enter the Functions themselves,
+        so each ``weight.grad`` / ``bias.grad`` arrives once, in the parameter's shape and dtype; the packed images come from
+        the module's cache, which follows the parameters' versions.  The image gets no gradient."""
+        from . import autograd_ops as A
+
+        if cond_nchw.requires_grad:
+            raise NotImplementedError(COND_IMAGE_GRAD_MSG)
+        if cond_nchw.dtype not in ops.DT_ANY or not cond_nchw.is_contiguous():
+            cond_nchw = cond_nchw.float().contiguous()
+        convs = [self.conv_in] + list(self.blocks)
+        x = cond_nchw
+        for i, conv in enumerate(convs):
+            s, img = conv.stride[0], i == 0
+            w, b = one(self._pk, R.cond_conv3x3(img, bgr), conv, dtype)
+            w_rot = None if img or not x.requires_grad else one(self._pk, R.cond_conv3x3_rot, conv, dtype)
+            x = A.SiLU.apply(A.CondConv3x3.apply(x, conv.weight, conv.bias, w, b, w_rot, s, img, bgr and img, dtype))
+        return x
+
+
+COND_IMAGE_GRAD_MSG = ("controlnet_cond requires a gradient, but the conditioning embedding's first layer has no input gradient on "
+                       "the MI355X path (it reads the caller's image as it lies in memory): pass the image without requires_grad")

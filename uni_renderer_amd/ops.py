@@ -592,6 +592,78 @@ def cond_conv3x3(x, w, bias, *, n_out, stride=1, act=ACT_NONE, dtype=None, image
     return out
 
 
+def cond_conv3x3_dgrad(dy, w_rot, *, in_hw, n_in, stride=1, out=None):
+    """Input gradient of ``cond_conv3x3`` (``ur_cond_conv3x3_dgrad``): NHWC ``dy`` [B, Ho, Wo, Cout] -> dx [B, H, W, n_in] with
+    ``in_hw`` = (H, W) the forward's input size (odd sizes with stride 2 included).  ``w_rot``: the image of
+    ``layers.pack_cond_conv3x3_rot`` of the layer's weight.  fp32 accumulation, one rounding; the image-mode first layer has no
+    input gradient."""
+    _require_gpu(dy)
+    lib = _lib.load()
+    if dy.dim() != 4 or not dy.is_contiguous() or dy.dtype not in DT:
+        raise ValueError("cond_conv3x3_dgrad: dy is a contiguous NHWC tensor in the compute dtype (fp16 / bf16)")
+    B, Ho, Wo, Cout = dy.shape
+    H, W = (int(v) for v in in_hw)
+    if stride not in (1, 2) or (Ho, Wo) != ((H - 1) // stride + 1, (W - 1) // stride + 1):
+        raise ValueError(f"cond_conv3x3_dgrad: a {(H, W)} input with stride {stride} does not give a {(Ho, Wo)} output")
+    if w_rot.dtype != dy.dtype or not w_rot.is_contiguous() or w_rot.numel() != cond_conv_weight_numel(Cout, n_in, 1, False):
+        raise ValueError("cond_conv3x3_dgrad: w_rot is the layers.pack_cond_conv3x3_rot image of this layer in the compute dtype")
+    if out is None:
+        out = torch.empty(B, H, W, n_in, dtype=dy.dtype, device=dy.device)
+    elif tuple(out.shape) != (B, H, W, n_in) or out.dtype != dy.dtype or not out.is_contiguous():
+        raise ValueError("cond_conv3x3_dgrad: out is a contiguous [B, H, W, n_in] tensor in the compute dtype")
+    e0 = _prof_begin()
+    check(lib.ur_cond_conv3x3_dgrad(dy.data_ptr(), w_rot.data_ptr(), out.data_ptr(), B, H, W, int(n_in), Cout, int(stride),
+                                    DT[dy.dtype], _stream()), "ur_cond_conv3x3_dgrad")
+    _prof_end(e0, "cond_conv3x3_dgrad", 2.0 * dy.numel() * 9 * n_in, float((dy.numel() + out.numel() + w_rot.numel()) * dy.element_size()))
+    return out
+
+
+def cond_conv3x3_wgrad(x, dy, *, stride=1, image=False, need_dw=True, need_bias=True, splits=0, dw_out=None, db_out=None):
+    """Weight and bias gradient of ``cond_conv3x3`` (``ur_cond_conv3x3_wgrad``): ``x`` as the forward read it (NHWC in the compute
+    dtype, or with ``image`` the caller's NCHW tensor [B, 1..4, H, W] in fp16 / bf16 / fp32), NHWC ``dy`` [B, Ho, Wo, Cout] ->
+    (dw [Cout, Cin, 3, 3] fp32 | None, db [Cout] fp32 | None), overwritten.  ``splits``: 0 = the kernel's own split of the pixels,
+    > 0 forces the count; a result is bit-reproducible for a given ``splits``.  The fp32 partials live in a workspace from
+    torch's allocator, so the call can be captured in a graph."""
+    _require_gpu(x)
+    lib = _lib.load()
+    if x.dim() != 4 or not x.is_contiguous() or dy.dim() != 4 or not dy.is_contiguous() or dy.dtype not in DT:
+        raise ValueError("cond_conv3x3_wgrad: x and dy are contiguous 4-d tensors, dy NHWC in the compute dtype (fp16 / bf16)")
+    dtype = dy.dtype
+    if image:
+        B, Cin, H, W = x.shape
+        if x.dtype not in DT_ANY:
+            raise ValueError("cond_conv3x3_wgrad: an fp16 / bf16 / fp32 image")
+    else:
+        B, H, W, Cin = x.shape
+        if x.dtype != dtype:
+            raise ValueError("cond_conv3x3_wgrad: an NHWC input is in the compute dtype of dy")
+    Cout = dy.shape[-1]
+    if stride not in (1, 2) or tuple(dy.shape[:3]) != (B, (H - 1) // stride + 1, (W - 1) // stride + 1):
+        raise ValueError(f"cond_conv3x3_wgrad: dy {tuple(dy.shape)} is not the output of x {tuple(x.shape)} with stride {stride}")
+    if not (need_dw or need_bias):
+        raise ValueError("cond_conv3x3_wgrad: nothing to compute")
+    splits = int(splits)
+    nbytes = lib.ur_cond_conv3x3_wgrad_workspace(B, H, W, Cin, Cout, int(stride), int(image), splits)
+    check(min(nbytes, 0), "ur_cond_conv3x3_wgrad_workspace")
+    dw = db = None
+    if need_dw:
+        dw = dw_out if dw_out is not None else torch.empty(Cout, Cin, 3, 3, dtype=torch.float32, device=x.device)
+        if tuple(dw.shape) != (Cout, Cin, 3, 3) or dw.dtype != torch.float32 or not dw.is_contiguous():
+            raise ValueError("cond_conv3x3_wgrad: dw is a contiguous fp32 [Cout, Cin, 3, 3] tensor")
+    if need_bias:
+        db = db_out if db_out is not None else torch.empty(Cout, dtype=torch.float32, device=x.device)
+        if tuple(db.shape) != (Cout,) or db.dtype != torch.float32 or not db.is_contiguous():
+            raise ValueError("cond_conv3x3_wgrad: db is a contiguous fp32 [Cout] tensor")
+    ws = torch.empty(nbytes // 4, dtype=torch.float32, device=x.device)
+    e0 = _prof_begin()
+    check(lib.ur_cond_conv3x3_wgrad(x.data_ptr(), DT_ANY[x.dtype], int(image), dy.data_ptr(), dw.data_ptr() if need_dw else None,
+                                    db.data_ptr() if need_bias else None, ws.data_ptr(), nbytes, B, H, W, Cin, Cout, int(stride),
+                                    splits, DT[dtype], _stream()), "ur_cond_conv3x3_wgrad")
+    _prof_end(e0, "cond_conv3x3_wgrad", 2.0 * dy.numel() * 9 * Cin,
+              float(x.numel() * x.element_size() + dy.numel() * dy.element_size() + 2 * nbytes))
+    return dw, db
+
+
 # conv -> GroupNorm (+ SiLU) with the normalisation as the split-K second pass (ur_igemm_splitk_gn).  OFF by default: parity is
 # green (tests/test_ops_gpu.py), but the step is 0.07 ms SLOWER with it (85.42 / 85.65 -> 85.01 / 84.92 steps/s alternating
 # on one box, profiles/r04_splitk_gn_ab.txt).  Round 4 blamed the 160-byte runs in which one workgroup per (sample, group) reads

@@ -70,7 +70,7 @@ def rows(recipe: Recipe) -> Recipe:
 
 
 # ---------------------------------------------------------------------------------------------------- the recipes
-from .layers import LOG2E, f32, geglu_perm, pack_cond_conv3x3, pack_conv3x3, pack_matrix  # noqa: E402 -- layers imports the cache above
+from .layers import LOG2E, f32, geglu_perm, pack_cond_conv3x3, pack_cond_conv3x3_rot, pack_conv3x3, pack_matrix  # noqa: E402 -- layers imports the cache above
 
 _wb = lambda m: (m.weight, m.bias)
 _scaled = lambda t, scale: (t * scale).contiguous() if scale != 1.0 else t
@@ -136,6 +136,11 @@ def cond_conv3x3(image: bool, bgr: bool) -> Recipe:
     """A conv of the ControlNet conditioning embedding in the weight image ``ops.cond_conv3x3`` reads."""
     return Recipe("cond_conv3x3", _wb, lambda m, dt, img, flip: (
         pack_cond_conv3x3(m.weight, dt, m.stride[0], image=img, bgr=flip), f32(m.bias)), (image, bgr and image))
+
+
+# The same conv's rotated, channel-transposed weights in the image ``ops.cond_conv3x3_dgrad`` reads (the weight alone: the input
+# gradient has no bias)
+cond_conv3x3_rot = Recipe("cond_conv3x3_rot", lambda m: (m.weight,), lambda m, dt: pack_cond_conv3x3_rot(m.weight, dt))
 
 
 # The three chain launches of a one-block 320-channel Transformer2DModel ``t`` (tchain.py): (weight stream, fp32 constants).

@@ -76,15 +76,20 @@ class _batched_casts:
                     for w in (m.attn2.to_k.weight, m.attn2.to_v.weight)]
             first = {id(w) for w in temb + ctxw}
             ws = temb + ctxw + [w for w in ws if id(w) not in first]
+            # the seven narrow convs of a ControlNet's conditioning embedding take no part: autograd_ops.CondConv3x3 reads the
+            # parameters themselves and returns their gradients in the parameters' own layout (no cast, no pack, no barrier)
+            emb = getattr(self.net, "controlnet_cond_embedding", None)
+            narrow = {id(m) for m in ([emb.conv_in] + list(emb.blocks))} if emb is not None else set()
             bs = [m.bias for m in self.net.modules()
                   if (isinstance(m, torch.nn.Linear) or (isinstance(m, torch.nn.Conv2d) and m.kernel_size in ((1, 1), (3, 3))))
-                  and m.bias is not None and m.bias.dtype == torch.float32]
+                  and m.bias is not None and m.bias.dtype == torch.float32 and id(m) not in narrow]
             # gamma / beta of the norm layers too: their gradients are summed in one launch at the barrier (backward.NormSums)
             bs += [p_ for m in self.net.modules() if isinstance(m, (torch.nn.GroupNorm, torch.nn.LayerNorm)) and m.weight is not None
                    for p_ in (m.weight, m.bias) if p_ is not None and p_.dtype == torch.float32]
             conv_in = getattr(self.net, "conv_in", None)
             c3 = [(m.weight, CIN_PAD if m is conv_in else None) for m in self.net.modules()
-                  if isinstance(m, torch.nn.Conv2d) and m.kernel_size == (3, 3) and m.weight.dtype == torch.float32]
+                  if isinstance(m, torch.nn.Conv2d) and m.kernel_size == (3, 3) and m.weight.dtype == torch.float32
+                  and id(m) not in narrow]
             hit = _castable[id(self.net)] = (self.net, [w for w in ws if w.dtype == torch.float32], bs, c3)
         ws = [w for w in hit[1] if w.requires_grad]
         if ws:
@@ -338,13 +343,46 @@ def encoder_forward(enc, cond_nhwc, ehs, t_attr, dt, conditioning_scale: float =
     with _batched_casts(enc, dt):
         te = _time(enc, t_attr, B, dt, dev)
         xe = _conv(enc.conv_in, cond_nhwc, dt, cin_pad=CIN_PAD)
-        raw_mid_enc, raw_enc = _down_mid(enc, xe, te, ehs, dt)
-        res = [A.linear(s, _w2(z, dt), z.bias) for s, z in zip(raw_enc, enc.controlnet_down_blocks)]
-        mid_res = A.linear(raw_mid_enc, _w2(enc.controlnet_mid_block, dt), enc.controlnet_mid_block.bias)
+        res, mid_res, raw_enc, raw_mid_enc = _encoder_trunk(enc, xe, te, ehs, dt)
     if conditioning_scale != 1.0:  # ref 1773-1775
         res = [r * conditioning_scale for r in res]
         mid_res = mid_res * conditioning_scale
     return res, mid_res, raw_enc, raw_mid_enc
+
+
+def _encoder_trunk(net, x, te, ehs, dt):
+    """Down blocks, mid block and the 12 + 1 exchange (``controlnet_*``) convs of an encoder-shaped network, from the output of its
+    input stage on: what AttributeEncoderModel and ControlNetModel share.  Inside the caller's ``_batched_casts``."""
+    raw_mid, raw = _down_mid(net, x, te, ehs, dt)
+    res = [A.linear(s, _w2(z, dt), z.bias) for s, z in zip(raw, net.controlnet_down_blocks)]
+    mid_res = A.linear(raw_mid, _w2(net.controlnet_mid_block, dt), net.controlnet_mid_block.bias)
+    return res, mid_res, raw, raw_mid
+
+
+def controlnet_forward(cn, x_nhwc, cond_nchw, ehs, t, dt, conditioning_scale: float = 1.0, guess_mode: bool = False):
+    """ControlNetModel (ref 2530-3266) under autograd: the conditioning embedding on the direct narrow-channel kernels
+    (layers.ControlNetConditioningEmbedding.forward_autograd), its ``conv_out`` as the residual operand of ``conv_in(sample)``,
+    then the trunk of ``encoder_forward``.  ``x_nhwc`` [B,H,W,CIN_PAD]; ``cond_nchw`` the caller's image (no gradient).  The
+    scales are host floats: ``conditioning_scale``, times ``logspace(-1, 0, 13)`` in ``guess_mode`` (ref 3245-3249).  Returns
+    (res[12], mid_res), NHWC.  Not covered here: ``GraphedTrainStep`` (built around the three-network batch),
+    ``parallel.GradientBuckets`` / ``GradSink`` for this network, and LoRA on it."""
+    B, dev = x_nhwc.shape[0], x_nhwc.device
+    emb = cn.controlnet_cond_embedding
+    bgr = cn.config["controlnet_conditioning_channel_order"] == "bgr"
+    with _batched_casts(cn, dt):
+        te = _time(cn, t, B, dt, dev)
+        h = emb.forward_autograd(cond_nchw, dt, bgr=bgr)
+        if tuple(h.shape[:3]) != tuple(x_nhwc.shape[:3]):
+            raise ValueError(f"controlnet_cond {tuple(cond_nchw.shape)} embeds to a {tuple(h.shape[1:3])} map for a "
+                             f"{tuple(x_nhwc.shape[1:3])} sample")
+        e = _conv(emb.conv_out, h, dt)
+        x = A.conv3x3(x_nhwc, A.pack_conv_weight(cn.conv_in.weight, dt, CIN_PAD), cn.conv_in.bias, res=e)  # ref 3201-3204
+        res, mid_res, _, _ = _encoder_trunk(cn, x, te, ehs, dt)
+    s, n = float(conditioning_scale), len(res) + 1
+    scales = [10.0 ** (-1.0 + i / (n - 1)) * s for i in range(n)] if guess_mode else [s] * n
+    res = [r if k == 1.0 else r * k for r, k in zip(res, scales)]
+    mid_res = mid_res if scales[-1] == 1.0 else mid_res * scales[-1]
+    return res, mid_res
 
 
 def unet_forward(unet, x_nhwc, ehs, t_img, dt, res=None, mid_res=None, collect_up: bool = False, lora_scale=None):
