@@ -32,6 +32,8 @@
  *   ur_nchw_to_nhwc / ur_nhwc_to_nchw   layout glue at the module boundary (the reference is NCHW).
  *   ur_ddim_update / ur_unipc_update / ur_sampler_advance   the per-group scheduler `.step()` calls and the timestep bookkeeping between
  *                   two denoise steps of the sampling loops (models/pipeline.py:2691-2730, 1645-1649), on the device.
+ *   ur_sde_update / ur_sampler_noise   the same for the stochastic schedulers (DDIM with eta, DDPM, SDE-DPM-Solver++) and
+ *                   DPM-Solver++: the `randn_tensor` of their `.step()` drawn inside the update kernel.
  *   ur_freeu        diffusers' apply_freeu in front of `torch.cat([hidden, skip])` of the first two up blocks
  *                   (models/unet_2d_blocks.py:2343-2370, 2522-2546, 2653-2677, 2767-2790): the in-place backbone scale
  *                   `hidden[:, : C // 2] *= b` and fourier_filter's fftn -> fftshift -> box * s -> ifftshift -> ifftn -> real
@@ -604,6 +606,30 @@ int ur_select_step_rows(const void* const* src, void* const* dst, const int64_t*
 int ur_unipc_update(const void* pred, int pred_ld, int pred_c0, void* lat, int64_t lat_bstride, int C, int B, int HW,
                     const float* coef, const int* step, int nsteps, float* last, float* xmaster, float* hist,
                     int round_master, int cfg, float guidance, int cfg_channels, int dtype, void* stream);
+
+/*
+ * ur_sde_update (csrc/sampler_sde.hip; an ADDITION to ABI 17, nothing existing changes): the update of the samplers that are a
+ * linear multistep recurrence with a noise term for an x0-predicting model -- DDIM with eta, DDPM (fixed_small / fixed_large),
+ * DPM-Solver++ 1 / 2M and SDE-DPM-Solver++ 1 / 2M (host: the coefficient_table() of schedulers.DDIMScheduler, DDPMScheduler,
+ * DPMSolverMultistepScheduler, row i = p0 p1 p2 pn, fp32 [nsteps][4]):
+ *     x_{i+1} = p0 x_i + p1 m_i + p2 m_{i-1} + pn xi_i,   i = min(max(*step, 0), nsteps - 1),   m_i = pred (after the cfg combine)
+ * The products are added left to right in fp32 without fma contraction; a row with pn == 0 has three terms, draws no noise and
+ * does not read *seed.  pred / lat / lat_bstride / cfg / guidance / cfg_channels / round_master / dtype as ur_ddim_update, and
+ * dtype may also be UR_DT_F32.  master: fp32 [B][C][HW], REQUIRED: x is read from it and the new x stored there (through the
+ * storage dtype first if round_master), its rounding in lat (both halves under cfg).  hist: fp32 [B][C][HW], m_{i-1}; zeroed by
+ * the caller before step 0 (row 0 has p2 = 0); m_i is stored there.  The caller advances *step with ur_sampler_advance.
+ * Noise: xi_i is a standard normal per element e of the logical contiguous [B][C][HW] latent, a function of (*seed, i, e) only:
+ * group g = e / 4 runs Philox4x32-10 with counter (g & 0xffffffff, g >> 32, i, 0) and key (seed & 0xffffffff, seed >> 32); the
+ * output words give u_k = ((w_k >> 8) + 0.5) * 2^-24; z0 = r cos t, z1 = r sin t with r = sqrt(-2 ln u_0), t = 2 pi u_1; z2, z3
+ * likewise from u_2, u_3; element e takes z[e % 4].  seed: ONE device int64, read by the kernel -- a captured graph bakes in
+ * its address, never its value.  UR_E_BADARG: a null pointer, sizes <= 0, pred_c0 + C > pred_ld, lat_bstride < C * HW,
+ * cfg_channels outside [0, C], an unknown dtype.
+ * ur_sampler_noise: out[e] = xi_step[e] for e in [0, n), the same stream (the same device function) as a fp32 tensor.
+ */
+int ur_sde_update(const void* pred, int pred_ld, int pred_c0, void* lat, int64_t lat_bstride, int C, int B, int HW,
+                  const float* coef, const int* step, int nsteps, const int64_t* seed, float* master, float* hist,
+                  int round_master, int cfg, float guidance, int cfg_channels, int dtype, void* stream);
+int ur_sampler_noise(const int64_t* seed, int step, float* out, int64_t n, void* stream);
 
 /*
  * Weight prefetch into the 256 MB Infinity Cache (MI355X's memory-side last-level cache).  One denoise step reads

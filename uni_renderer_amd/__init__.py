@@ -9,7 +9,7 @@ from .controlnet import (AttributeDecoderModel, AttributeEncoderModel, ControlNe
                          UNet2DConditionOutput)
 from .optim import AdamW8bit, FusedAdamW
 from .pipeline import UniRendererPipeline
-from .schedulers import DDIMScheduler, UniPCMultistepScheduler
+from .schedulers import DDIMScheduler, DDPMScheduler, DPMSolverMultistepScheduler, UniPCMultistepScheduler
 from .vae import AutoencoderKL
 from .unet_2d_blocks import (CrossAttnDownBlock2D, CrossAttnUpBlock2D, CrossAttnUpResBlock2D, DownBlock2D,
                              UNetMidBlock2DCrossAttn, UpBlock2D, UpResBlock2D, get_down_block, get_up_block)
@@ -19,6 +19,7 @@ __all__ = [
     "ControlNetModel", "ControlNetOutput",
     "CrossAttnDownBlock2D", "DownBlock2D", "UNetMidBlock2DCrossAttn", "UpBlock2D", "CrossAttnUpBlock2D",
     "UpResBlock2D", "CrossAttnUpResBlock2D", "get_down_block", "get_up_block",
-    "UniRendererPipeline", "AutoencoderKL", "DDIMScheduler", "UniPCMultistepScheduler", "FusedAdamW", "AdamW8bit",
+    "UniRendererPipeline", "AutoencoderKL", "DDIMScheduler", "UniPCMultistepScheduler", "DDPMScheduler",
+    "DPMSolverMultistepScheduler", "FusedAdamW", "AdamW8bit",
 ]
 __version__ = "0.1.0"

@@ -900,6 +900,64 @@ def unipc_update(pred_nhwc, c0: int, lat_nchw, coef, step, nsteps: int, last, xm
                               DT[lat_nchw.dtype], _stream()), "ur_unipc_update")
 
 
+def _seed_ptr(seed, what: str):
+    if seed.dtype != torch.int64 or seed.numel() != 1 or not seed.is_cuda:
+        raise RuntimeError(f"{what}: seed must be one int64 on the device")
+    import ctypes as C
+
+    return C.cast(seed.data_ptr(), C.POINTER(C.c_int64))
+
+
+def sde_update(pred_nhwc, c0: int, lat_nchw, coef, step, nsteps: int, seed, master, hist, round_master: bool = False,
+               guidance: Optional[float] = None, cfg_channels: int = 0):
+    """In-place update ``x <- p0 x + p1 m + p2 m_prev + pn xi`` of the NCHW latent slice ``lat_nchw`` from channels c0.. of the
+    NHWC prediction (include/ur_kernels.h ``ur_sde_update``): DDIM with eta, DDPM, (SDE-)DPM-Solver++.  ``coef`` [nsteps, 4]
+    from the scheduler's ``coefficient_table``; ``master`` / ``hist`` fp32 [B, C, H, W] (``hist`` zero before step 0);
+    ``seed`` one device int64 that keys the noise ``xi`` the kernel draws itself (``sampler_noise`` is the same stream).
+    fp16 / bf16 / fp32 latents.  ``guidance``: as in ``ddim_update``."""
+    _require_gpu(pred_nhwc)
+    lib = _lib.load()
+    B, Cc, H, W = lat_nchw.shape
+    cfg = guidance is not None
+    if cfg:
+        if B % 2 or pred_nhwc.shape[0] != B:
+            raise RuntimeError("sde_update: guidance needs cond + uncond halves")
+        B //= 2
+    if lat_nchw.stride(3) != 1 or lat_nchw.stride(2) != W or lat_nchw.stride(1) != H * W:
+        raise RuntimeError("sde_update: latent slice must have contiguous channel planes")
+    if (pred_nhwc.dtype != lat_nchw.dtype or lat_nchw.dtype not in DT_ANY or coef.dtype != torch.float32
+            or step.dtype != torch.int32 or coef.dim() != 2 or coef.shape[-1] != 4 or coef.shape[0] < nsteps
+            or not coef.is_contiguous()):
+        raise RuntimeError("sde_update: dtype / table mismatch")
+    if pred_nhwc.dim() != 4 or not pred_nhwc.is_contiguous() or tuple(pred_nhwc.shape[:3]) != (lat_nchw.shape[0], H, W):
+        raise RuntimeError("sde_update: pred must be a contiguous NHWC [B, H, W, Cp] tensor over the same samples and pixels")
+    if not 0 <= cfg_channels <= Cc:
+        raise RuntimeError("sde_update: cfg_channels outside [0, C]")
+    for t in (master, hist):
+        if t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != (B, Cc, H, W):
+            raise RuntimeError("sde_update: master / hist must be contiguous fp32 [B, C, H, W]")
+    check(lib.ur_sde_update(pred_nhwc.data_ptr(), pred_nhwc.shape[-1], c0, lat_nchw.data_ptr(), lat_nchw.stride(0), Cc, B,
+                            H * W, coef.data_ptr(), step.data_ptr(), nsteps, _seed_ptr(seed, "sde_update"), master.data_ptr(),
+                            hist.data_ptr(), int(round_master), int(cfg), float(guidance or 0.0), int(cfg_channels),
+                            DT_ANY[lat_nchw.dtype], _stream()), "ur_sde_update")
+
+
+def sampler_noise(seed, step: int, shape, out=None):
+    """fp32 tensor of ``shape`` holding the noise ``ur_sde_update`` draws at step ``step`` under the device int64 ``seed`` for
+    a latent of that (logical, contiguous) shape: the package's own Philox stream (include/ur_kernels.h), not torch.randn's."""
+    _require_gpu(seed)
+    lib = _lib.load()
+    if out is None:
+        out = torch.empty(tuple(shape), dtype=torch.float32, device=seed.device)
+    if out.dtype != torch.float32 or not out.is_contiguous() or tuple(out.shape) != tuple(shape) or out.numel() == 0:
+        raise RuntimeError("sampler_noise: out must be a non-empty contiguous fp32 tensor of `shape`")
+    if int(step) < 0:
+        raise RuntimeError("sampler_noise: step < 0")
+    check(lib.ur_sampler_noise(_seed_ptr(seed, "sampler_noise"), int(step), out.data_ptr(), out.numel(), _stream()),
+          "ur_sampler_noise")
+    return out
+
+
 def sampler_advance(step, tsteps, nsteps: int, t_out=None):
     lib = _lib.load()
     check(lib.ur_sampler_advance(step.data_ptr(), tsteps.data_ptr(), nsteps, _ptr(t_out),

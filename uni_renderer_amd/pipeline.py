@@ -267,18 +267,18 @@ class UniRendererPipeline:
     # ---- one denoise step of the three networks ----------------------------------------------------------
     # ---- on-device sampling loop -------------------------------------------------------------
     def _fusable(self, scheds, device, cond_scale, callback) -> bool:
-        """The fused loop covers what eval needs: this package's DDIM (x0 prediction) or UniPC (order <= 2, x0
-        prediction, bh2 -- the scheduler eval/test_real.py:485-492 attaches) on every latent group with one common
-        schedule, with or without classifier-free guidance, no per-step callback, HIP graph on.  Anything else takes
+        """The fused loop covers what eval needs: this package's DDIM (x0 prediction, any eta), UniPC (order <= 2, x0
+        prediction, bh2 -- the scheduler eval/test_real.py:485-492 attaches), DDPM or DPM-Solver++ on every latent group with
+        one common schedule and configuration, with or without classifier-free guidance, no per-step callback, HIP graph on.  Anything else takes
         the step-by-step loop below (identical results: tests/test_pipeline_gpu.py)."""
-        from .schedulers import DDIMScheduler, UniPCMultistepScheduler
+        from .schedulers import DDIMScheduler, DDPMScheduler, DPMSolverMultistepScheduler, UniPCMultistepScheduler
 
         if not (self.use_fused_sampler and self.use_hip_graph and torch.device(device).type == "cuda"):
             return False
         if callback is not None:
             return False
         s0 = scheds[0]
-        if type(s0) not in (DDIMScheduler, UniPCMultistepScheduler):
+        if type(s0) not in (DDIMScheduler, UniPCMultistepScheduler, DDPMScheduler, DPMSolverMultistepScheduler):
             return False
         for s in scheds:
             if type(s) is not type(s0) or s.prediction_type != "sample":
@@ -289,9 +289,62 @@ class UniRendererPipeline:
                 return False
             if type(s0) is DDIMScheduler and float(s.final_alpha_cumprod) != float(s0.final_alpha_cumprod):
                 return False
-            if type(s0) is UniPCMultistepScheduler and s.config != s0.config:
+            if type(s0) is not DDIMScheduler and s.config != s0.config:
                 return False
         return True
+
+    # ---- stochastic samplers (DDIM with eta, DDPM, SDE-DPM-Solver++) and DPM-Solver++ ------------------------------
+    @staticmethod
+    def _sde_table(sched, eta: float):
+        """The [n, 4] table of ``ur_sde_update`` for ``sched``, or None where the loops keep their existing update (DDIM with
+        eta = 0, UniPC, a foreign scheduler object)."""
+        from .schedulers import DDIMScheduler, DDPMScheduler, DPMSolverMultistepScheduler
+
+        if type(sched) is DDIMScheduler:
+            return sched.coefficient_table(eta) if eta != 0.0 else None
+        if type(sched) in (DDPMScheduler, DPMSolverMultistepScheduler):
+            return sched.coefficient_table()
+        return None
+
+    def _draw_seed(self, scheds, eta: float, generator) -> Optional[int]:
+        """ONE int64 per sampling call that keys the noise of every step (``ur_sde_update``, ``ops.sampler_noise``,
+        ``schedulers.philox_normal``), drawn from ``generator`` (the global generator if None) -- the package's own stream, not
+        ``torch.randn``'s: the same ``manual_seed`` gives the same images, a second call on the same generator object other
+        ones.  None, and nothing drawn, when no scheduler of the call has a noise term."""
+        noisy = False
+        for s in scheds:
+            tab = self._sde_table(s, eta)
+            noisy = noisy or (tab is not None and bool((tab[:, 3] != 0).any()))
+        if not noisy:
+            return None
+        if isinstance(generator, (list, tuple)):
+            generator = generator[0]
+        return int(torch.randint(0, 2 ** 63 - 1, (1,), generator=generator, dtype=torch.int64,
+                                 device=generator.device if generator is not None else "cpu"))
+
+    @staticmethod
+    def _step_noise(seed: Optional[int], seed_dev, i: int, shape, device):
+        """The noise of step ``i`` of the step-by-step loops for the whole evolving latent of ``shape`` (what the fused loop's
+        kernel draws for the same elements), or None for a call without a noise term."""
+        if seed is None:
+            return None
+        if torch.device(device).type == "cuda":
+            return ops.sampler_noise(seed_dev, i, shape)
+        from .schedulers import philox_normal
+
+        return philox_normal(seed, i, shape).to(device)
+
+    @staticmethod
+    def _step_kwargs(sched, eta: float, noise) -> Dict[str, Any]:
+        """ref ``prepare_extra_step_kwargs``: eta goes to the DDIM scheduler only; the noise to the classes that take it."""
+        from .schedulers import DDIMScheduler, DDPMScheduler, DPMSolverMultistepScheduler
+
+        kw: Dict[str, Any] = {}
+        if type(sched) is DDIMScheduler and eta != 0.0:
+            kw["eta"] = eta
+        if noise is not None and type(sched) in (DDIMScheduler, DDPMScheduler, DPMSolverMultistepScheduler):
+            kw["variance_noise"] = noise
+        return kw
 
     @staticmethod
     def _ddim_tables(sched, timesteps):
@@ -341,9 +394,11 @@ class UniRendererPipeline:
         return key, g
 
     def _fused_loop(self, x_img, cond28, ehs, timesteps, sched, run_decoder: bool, lat_dtype=torch.float32,
-                    guidance: Optional[float] = None, cond_scale: float = 1.0):
+                    guidance: Optional[float] = None, cond_scale: float = 1.0, eta: float = 0.0, seed: Optional[int] = None):
         """All denoise steps as replays of ONE graph = step + ur_ddim_update (prediction -> next input, in the
-        graph's static input buffer) + ur_sampler_advance (step counter, next timestep).  Inverse direction: the 24
+        graph's static input buffer) + ur_sampler_advance (step counter, next timestep).  UniPC: ur_unipc_update.  DDIM
+        with eta != 0, DDPM, (SDE-)DPM-Solver++: ur_sde_update, whose noise is keyed by ``seed``, written into a device
+        buffer before the replays (the graph knows the buffer, not the value).  Inverse direction: the 24
         attribute channels of ``cond`` evolve at t_attr, the image latent is clean (t_img = 0); rendering direction:
         the 4 image channels of ``x_t`` evolve at t_img, the attributes are clean.  ``guidance``: classifier-free
         guidance -- the inputs hold cond + uncond halves (2B samples); the inverse direction guides the material group
@@ -357,11 +412,16 @@ class UniRendererPipeline:
         from .schedulers import UniPCMultistepScheduler
 
         unipc = type(sched) is UniPCMultistepScheduler
+        sde_table = self._sde_table(sched, eta)
+        sde = sde_table is not None
         if unipc:
             coef, tvals = sched.coefficient_table(), timesteps.detach().cpu().to(torch.float32)
+        elif sde:
+            coef, tvals = sde_table, timesteps.detach().cpu().to(torch.float32)
         else:
             coef, tvals = self._ddim_tables(sched, timesteps)
-        skey = key + (n, lat_dtype, guidance, self.precompute_time_tables, "unipc" if unipc else "ddim")
+        kind = "unipc" if unipc else ("sde-" + type(sched).__name__ if sde else "ddim")
+        skey = key + (n, lat_dtype, guidance, self.precompute_time_tables, kind)
         st = self._sample_graphs.get(skey)
         if st is None:
             dev = x_img.device
@@ -374,9 +434,15 @@ class UniRendererPipeline:
             if unipc:  # corrected sample L and the two previous predictions (ur_unipc_update)
                 st["last"] = torch.zeros(mshape, dtype=torch.float32, device=dev)
                 st["hist"] = torch.zeros((2,) + mshape, dtype=torch.float32, device=dev)
+            if sde:  # the previous prediction and the noise key (ur_sde_update)
+                st["hist"] = torch.zeros(mshape, dtype=torch.float32, device=dev)
+                st["seed"] = torch.zeros(1, dtype=torch.int64, device=dev)
 
             def update(pred_nhwc, c0, lat, cfg_channels):
-                if unipc:
+                if sde:
+                    ops.sde_update(pred_nhwc, c0, lat, st["coef"], st["step"], n, st["seed"], st["master"], st["hist"],
+                                   round_master=st["round_master"], guidance=guidance, cfg_channels=cfg_channels)
+                elif unipc:
                     ops.unipc_update(pred_nhwc, c0, lat, st["coef"], st["step"], n, st["last"], st["master"], st["hist"],
                                      round_master=st["round_master"], guidance=guidance, cfg_channels=cfg_channels)
                 else:
@@ -407,6 +473,9 @@ class UniRendererPipeline:
         if unipc:
             st["last"].copy_(st["master"])  # L_0 = the initial sample
             st["hist"].zero_()
+        if sde:
+            st["hist"].zero_()
+            st["seed"].fill_(0 if seed is None else seed)
         hoisted = isinstance(g, GraphedHoistedStep)
         if st.get("tgraph") is not None:
             st["tgraph"].replay()  # time projections of every step of this call (st["tvals"] was written above)
@@ -448,7 +517,10 @@ class UniRendererPipeline:
         """Inverse rendering: image (+ mask) -> material / normal / albedo / specular / diffuse / environment.
         Returns ``(material_latents, normal, albedo, spec_light, diff_light, env)`` like the reference (2808).
         ``image_latents`` / ``mask_latents`` (already VAE-encoded, scaled) bypass the VAE; ``output_type="latent"``
-        returns the six latents instead of decoded images."""
+        returns the six latents instead of decoded images.  ``eta`` is DDIM's (other schedulers ignore it, as in the
+        reference's ``prepare_extra_step_kwargs``).  A sampler with a noise term (DDIM with eta != 0, DDPM, SDE-DPM-Solver++)
+        draws ONE int64 from ``generator`` per call and takes all its noise from the package's own counter-based stream
+        keyed by it (``_draw_seed``) -- reproducible under ``manual_seed``, not ``torch.randn``'s numbers."""
         self._guidance_scale = guidance_scale
         self.unet._lora_apply(scale_of(cross_attention_kwargs))  # before any _weights_signature(): graphs see merged weights
         device = self._execution_device
@@ -496,15 +568,18 @@ class UniRendererPipeline:
         cond_scale = float(controlnet_conditioning_scale)
 
         group_scheds = [getattr(self, f"scheduler_{n}") for n in ATTR_GROUPS]
+        eta = float(eta)
+        seed = self._draw_seed(group_scheds, eta, generator)  # after the initial latents, in both loops: same generator state
         if self._fusable([self.scheduler_attr] + group_scheds, device, cond_scale, callback_on_step_end):
             cat = torch.cat([dup(lat[n]) for n in ATTR_GROUPS], dim=1)
             cond28 = torch.cat((x_mask.to(cat.dtype), cat), dim=1)
             fin = self._fused_loop(x_img, cond28, prompt_embeds, timesteps_attr, group_scheds[0], run_decoder=True,
                                    lat_dtype=cat.dtype, guidance=(float(self.guidance_scale) if cfg else None),
-                                   cond_scale=cond_scale)
+                                   cond_scale=cond_scale, eta=eta, seed=seed)
             lat = {n: fin[:, 4 * k:4 * k + 4].to(lat[n].dtype) for k, n in enumerate(ATTR_GROUPS)}
             timesteps_img = timesteps_attr = []  # loop below is skipped
         sig = self._weights_signature() if len(timesteps_attr) else None  # once per call, not per step
+        seed_dev = torch.tensor([seed], dtype=torch.int64, device=device) if seed is not None and len(timesteps_attr) else None
         with self.progress_bar(total=num_inference_steps) as bar:
             # the clean image latent's timestep is the constant 0 (ref 2476): hand the hoisted executor the SAME tensor object on every
             # step -- it re-runs its prologue when a fixed input changes identity (graph.GraphedHoistedStep.step), and the per-step
@@ -518,13 +593,17 @@ class UniRendererPipeline:
                 out = self._step(x_img, cond28, prompt_embeds, t_img, t_attr, run_decoder=True, cond_scale=cond_scale, sig=sig,
                                  first=(i == 0))
                 label_pred = out["attr_pred"][:, 4:]  # drop the mask group (ref 2691)
+                # the six groups are ONE 24-channel latent to the noise stream, as in the fused loop
+                noise = self._step_noise(seed, seed_dev, i, (total, 4 * len(ATTR_GROUPS), h8, w8), device)
                 for k, n in enumerate(ATTR_GROUPS):
                     pred = label_pred[:, 4 * k:4 * k + 4]
                     if cfg:
                         # chunk order exactly as the reference reads it (2697-2721)
                         p_cond, p_uncond = pred.chunk(2)
                         pred = p_uncond + self.guidance_scale * (p_cond - p_uncond) if n == "material" else p_cond
-                    lat[n] = getattr(self, f"scheduler_{n}").step(pred, t_attr, lat[n], return_dict=False)[0]
+                    sch = getattr(self, f"scheduler_{n}")
+                    kw_step = self._step_kwargs(sch, eta, None if noise is None else noise[:, 4 * k:4 * k + 4])
+                    lat[n] = sch.step(pred, t_attr, lat[n], return_dict=False, **kw_step)[0]
                 if callback_on_step_end is not None:
                     callback_on_step_end(self, i, t_attr, {"latents": lat["material"]})
                 bar.update()
@@ -555,7 +634,8 @@ class UniRendererPipeline:
         attr_latents: Optional[torch.Tensor] = None, **kwargs,
     ):
         """Rendering: attributes -> image (enc + unet per step; the decoder is not run, ref 1631-1639).
-        ``attr_latents`` ([B,28,h,w], mask first) bypasses the VAE encodes of the seven attribute images."""
+        ``attr_latents`` ([B,28,h,w], mask first) bypasses the VAE encodes of the seven attribute images.  ``eta`` /
+        ``generator``: as in ``real_image2mask_3mod_albedo``."""
         self._guidance_scale = guidance_scale
         self.unet._lora_apply(scale_of(cross_attention_kwargs))  # before any _weights_signature(): graphs see merged weights
         device = self._execution_device
@@ -586,13 +666,16 @@ class UniRendererPipeline:
         cfg = self.do_classifier_free_guidance
         dup = (lambda t: torch.cat([t, t])) if cfg else (lambda t: t)
         cond28 = dup(self.scheduler_img.scale_model_input(attr_latents, 0))
+        eta = float(eta)
+        seed = self._draw_seed([self.scheduler_img], eta, generator)
         if self._fusable([self.scheduler_img], device, float(controlnet_conditioning_scale), None):
             latents_img = self._fused_loop(dup(latents_img), cond28, prompt_embeds, timesteps, self.scheduler_img,
                                            run_decoder=False, lat_dtype=latents_img.dtype,
                                            guidance=(float(self.guidance_scale) if cfg else None),
-                                           cond_scale=float(controlnet_conditioning_scale))
+                                           cond_scale=float(controlnet_conditioning_scale), eta=eta, seed=seed)
             timesteps = timesteps[:0]  # loop below is skipped
         sig = self._weights_signature() if len(timesteps) else None
+        seed_dev = torch.tensor([seed], dtype=torch.int64, device=device) if seed is not None and len(timesteps) else None
         with self.progress_bar(total=num_inference_steps) as bar:
             t_attr_fixed = timesteps_attr[0] if len(timesteps) else None  # clean attributes: the constant 0, one object (see above)
             for i in range(len(timesteps)):
@@ -604,7 +687,9 @@ class UniRendererPipeline:
                 if cfg:
                     p_cond, p_uncond = img_pred.chunk(2)  # ref 1642-1644
                     img_pred = p_uncond + self.guidance_scale * (p_cond - p_uncond)
-                latents_img = self.scheduler_img.step(img_pred, t_img, latents_img, return_dict=False)[0]
+                noise = self._step_noise(seed, seed_dev, i, tuple(latents_img.shape), device)
+                latents_img = self.scheduler_img.step(img_pred, t_img, latents_img, return_dict=False,
+                                                      **self._step_kwargs(self.scheduler_img, eta, noise))[0]
                 bar.update()
         if output_type == "latent":
             return latents_img

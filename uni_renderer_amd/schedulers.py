@@ -3,10 +3,19 @@
 The reference attaches eight ``UniPCMultistepScheduler`` instances to the pipeline (eval/test_real.py:485-492)
 and BASELINE.json's config 3 names a 50-step DDIM; both come from diffusers, which is not available here.  The
 pipeline only needs the diffusers scheduler *protocol* -- ``set_timesteps``, ``timesteps``, ``order``,
-``init_noise_sigma``, ``scale_model_input``, ``step(...)[0]``, ``add_noise`` -- so any diffusers scheduler can
-still be attached; this class is a DDIM (eta = 0) with the model's x0 ("sample") prediction on the
-SD scaled-linear beta schedule.  It is elementwise plumbing between denoise steps (SURVEY.md §8f rank 1 moves it
-into a fused HIP kernel), not part of the measured hot path.
+``init_noise_sigma``, ``scale_model_input``, ``step(...)[0]``, ``add_noise``.  The schedulers of this module are
+restatements of the published algorithms as diffusers 0.24 parameterises them, pinned by properties (parity with
+diffusers itself is unpinned): ``DDIMScheduler`` (eta = 0 and eta != 0) with the model's x0 ("sample") prediction
+ on the SD scaled-linear beta schedule, ``UniPCMultistepScheduler``, ``DDPMScheduler`` and
+``DPMSolverMultistepScheduler`` (DPM-Solver++ 1 / 2M and its SDE variant).  All of them run inside the fused sampling
+loop (one update kernel per step: ``ur_ddim_update``, ``ur_unipc_update``, ``ur_sde_update``); an object of another
+class that follows the protocol with ``init_noise_sigma == 1`` takes the step-by-step loop.  The Euler / Heun / PNDM
+families are refused by name (``NotImplementedError``).
+
+Noise: a stochastic sampler inside the pipeline draws from the package's own counter-based stream (``philox_normal``
+here, ``ops.sampler_noise`` / ``ur_sde_update`` on the device), keyed by ONE int64 drawn from the caller's generator
+per call -- not from ``torch.randn``'s stream.  A ``step`` called directly takes ``variance_noise`` or draws with
+``torch.randn(..., generator=generator)``.
 """
 from __future__ import annotations
 
@@ -23,6 +32,9 @@ class DDIMScheduler:
                  prediction_type: str = "sample", steps_offset: int = 1, set_alpha_to_one: bool = False):
         if prediction_type not in ("sample", "epsilon"):
             raise ValueError(prediction_type)
+        self.config = dict(num_train_timesteps=num_train_timesteps, beta_start=beta_start, beta_end=beta_end,
+                           beta_schedule="scaled_linear", prediction_type=prediction_type, steps_offset=steps_offset,
+                           set_alpha_to_one=set_alpha_to_one, clip_sample=False)
         self.num_train_timesteps = num_train_timesteps
         self.prediction_type = prediction_type
         self.steps_offset = steps_offset
@@ -45,8 +57,39 @@ class DDIMScheduler:
         t = torch.as_tensor(t, device="cpu").long().clamp(0, self.num_train_timesteps - 1)
         return self.alphas_cumprod[t].to(device)
 
-    def step(self, model_output: torch.Tensor, timestep, sample: torch.Tensor, return_dict: bool = False, **_):
+    def _alphas_at(self, t: int):
+        """(a_t, a_prev) as float64 Python numbers: the fp32 table values, exactly."""
+        prev_t = t - self.num_train_timesteps // (self.num_inference_steps or self.num_train_timesteps)
+        a_t = float(self._alpha(t, "cpu"))
+        a_prev = float(self._alpha(prev_t, "cpu")) if prev_t >= 0 else float(self.final_alpha_cumprod)
+        return a_t, a_prev
+
+    def _row64(self, t: int, eta: float):
+        """(p0, p1, p2, pn) of ``x_prev = p0 x + p1 x0 + p2 x0_prev + pn xi`` at timestep ``t`` in float64: DDIM (Song et al.
+        2021, eq. 12 / 16) with sigma = eta sqrt((1 - a_prev) / (1 - a_t)) sqrt(1 - a_t / a_prev), written for the x0 prediction
+        (eps = (x - sqrt(a_t) x0) / sqrt(1 - a_t) substituted)."""
+        a_t, a_prev = self._alphas_at(t)
+        sigma = float(eta) * ((1 - a_prev) / (1 - a_t)) ** 0.5 * max(1 - a_t / a_prev, 0.0) ** 0.5
+        p0 = max(1 - a_prev - sigma * sigma, 0.0) ** 0.5 / (1 - a_t) ** 0.5
+        return (p0, a_prev ** 0.5 - a_t ** 0.5 * p0, 0.0, sigma)
+
+    def coefficient_table(self, eta: float = 0.0) -> torch.Tensor:
+        """[n, 4] fp32 rows (p0, p1, p2, pn) over ``timesteps``: what ``ur_sde_update`` consumes and what ``step`` with
+        ``eta != 0`` evaluates (p2 = 0: DDIM is a one-step method).  The fused loop runs ``eta == 0`` on ``ur_ddim_update``."""
+        return torch.tensor([self._row64(int(t), eta) for t in self.timesteps.cpu().tolist()], dtype=torch.float32).reshape(-1, 4)
+
+    def step(self, model_output: torch.Tensor, timestep, sample: torch.Tensor, eta: float = 0.0, use_clipped_model_output=False,
+             generator=None, variance_noise: Optional[torch.Tensor] = None, return_dict: bool = False, **_):
+        """``eta == 0``: the deterministic step, unchanged.  ``eta != 0`` (a restatement of the published algorithm as
+        diffusers 0.24 parameterises it; parity with diffusers is unpinned, diffusers is not available here): the fp32 row of
+        ``coefficient_table(eta)`` evaluated left to right like ``ur_sde_update``; the noise is ``variance_noise`` if given,
+        else ``torch.randn(..., generator=generator)``."""
         t = int(torch.as_tensor(timestep).flatten()[0].item())
+        if eta != 0.0:
+            if use_clipped_model_output:
+                raise NotImplementedError("DDIMScheduler: use_clipped_model_output")
+            prev = _linear_step(self._row64(t, eta), self._to_x0(model_output, t, sample), sample, None, generator, variance_noise)
+            return (prev,) if not return_dict else {"prev_sample": prev}
         prev_t = t - self.num_train_timesteps // (self.num_inference_steps or self.num_train_timesteps)
         a_t = self._alpha(t, sample.device)
         a_prev = self._alpha(prev_t, sample.device) if prev_t >= 0 else self.final_alpha_cumprod.to(sample.device)
@@ -61,6 +104,13 @@ class DDIMScheduler:
         prev = a_prev.sqrt() * x0 + (1 - a_prev).sqrt() * eps
         prev = prev.to(sample.dtype)
         return (prev,) if not return_dict else {"prev_sample": prev}
+
+    def _to_x0(self, model_output, t: int, sample):
+        if self.prediction_type == "sample":
+            return model_output
+        cd = torch.float64 if sample.dtype == torch.float64 else torch.float32
+        a_t = self._alphas_at(t)[0]
+        return (sample.to(cd) - (1 - a_t) ** 0.5 * model_output.to(cd)) / a_t ** 0.5
 
     def add_noise(self, original: torch.Tensor, noise: torch.Tensor, timesteps: torch.Tensor) -> torch.Tensor:
         a = self.alphas_cumprod.to(original.device)[timesteps.long()].to(original.dtype)
@@ -300,3 +350,391 @@ class UniPCMultistepScheduler:
         while a.dim() < original.dim():
             a = a[..., None]
         return a.sqrt() * original + (1 - a).sqrt() * noise
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Samplers that are one linear multistep recurrence with a noise term (ur_sde_update):
+#     x_{i+1} = p0 x_i + p1 m_i + p2 m_{i-1} + pn xi_i          m_i = the model's x0 prediction at step i
+# DDIM with eta, DDPM, DPM-Solver++ (1, 2M) and SDE-DPM-Solver++ (1, 2M).  Each class computes its rows in float64
+# (``_rows64``), hands the kernel their fp32 rounding (``coefficient_table``) and evaluates ``step`` from the SAME fp32 row in
+# the kernel's order, so that the fused loop and the step-by-step loop agree bit for bit.
+# ---------------------------------------------------------------------------------------------------------------------
+def _linear_step(row64, m, sample, m_prev, generator, variance_noise):
+    """``p0 x + p1 m + p2 m_prev + pn xi``: products added left to right, separate multiply and add (no fma), in fp32 from
+    the fp32 rounding of ``row64`` -- float64 from ``row64`` itself when ``sample`` is float64 (the property tests) -- and one
+    rounding to ``sample.dtype``.  ``m_prev`` None = zeros.  ``pn == 0``: three terms, no noise drawn."""
+    import numpy as np
+
+    f64 = sample.dtype == torch.float64
+    cd = torch.float64 if f64 else torch.float32
+    p0, p1, p2, pn = (float(v) if f64 else float(np.float32(v)) for v in row64)
+    x, m = sample.to(cd), m.to(cd)
+    out = p0 * x
+    out = out + p1 * m
+    out = out + p2 * (torch.zeros_like(m) if m_prev is None else m_prev.to(cd))
+    if pn != 0.0:
+        if variance_noise is None:
+            gdev = generator.device if generator is not None else sample.device
+            variance_noise = torch.randn(sample.shape, generator=generator, device=gdev, dtype=cd)
+        if tuple(variance_noise.shape) != tuple(sample.shape):
+            raise ValueError(f"variance_noise has shape {tuple(variance_noise.shape)}, the sample {tuple(sample.shape)}")
+        out = out + pn * variance_noise.to(device=sample.device, dtype=cd)
+    return out.to(sample.dtype)
+
+
+def _betas(beta_schedule: str, beta_start: float, beta_end: float, n: int) -> torch.Tensor:
+    if beta_schedule == "scaled_linear":
+        return torch.linspace(beta_start ** 0.5, beta_end ** 0.5, n, dtype=torch.float32) ** 2
+    if beta_schedule == "linear":
+        return torch.linspace(beta_start, beta_end, n, dtype=torch.float32)
+    raise NotImplementedError(f"beta_schedule {beta_schedule!r}: scaled_linear and linear are implemented")
+
+
+def _config_of(config, cls):
+    c = dict(getattr(config, "config", config))
+    return {k: v for k, v in c.items() if not k.startswith("_")}
+
+
+class DDPMScheduler:
+    """DDPM ancestral sampling (Ho et al. 2020, eq. 7 and 11), restated from the published algorithm as diffusers 0.24's
+    ``DDPMScheduler`` parameterises it: ``variance_type`` ``fixed_small`` (the posterior variance, clamped at 1e-20) /
+    ``fixed_large`` (beta_t), no noise at t = 0, ``leading`` / ``linspace`` / ``trailing`` timestep spacing,
+    ``prediction_type`` ``epsilon`` / ``sample``.  diffusers is not available here, so parity with it is unpinned; the class is
+    pinned by properties (tests/test_stochastic_samplers_cpu.py): a ``fixed_small`` step == a DDIM eta = 1 step, the marginal
+    of a step under a perfect predictor, table == step arithmetic.  This is the noise scheduler the reference's training
+    script builds with ``DDPMScheduler.from_pretrained(path, subfolder="scheduler")`` (``add_noise``).
+
+    NOT implemented (``NotImplementedError``): ``clip_sample=True`` (so the default here is False, diffusers' is True),
+    ``thresholding``, the learned variance types, ``v_prediction``, custom timestep lists."""
+
+    order = 1
+    init_noise_sigma = 1.0
+
+    def __init__(self, num_train_timesteps: int = 1000, beta_start: float = 0.0001, beta_end: float = 0.02,
+                 beta_schedule: str = "linear", variance_type: str = "fixed_small", clip_sample: bool = False,
+                 prediction_type: str = "epsilon", thresholding: bool = False, timestep_spacing: str = "leading",
+                 steps_offset: int = 0, trained_betas=None, **_ignored):
+        if variance_type not in ("fixed_small", "fixed_large"):
+            raise NotImplementedError(f"DDPMScheduler: variance_type {variance_type!r} (fixed_small / fixed_large are implemented)")
+        if clip_sample or thresholding or trained_betas is not None:
+            raise NotImplementedError("DDPMScheduler: clip_sample, thresholding and trained_betas are not implemented")
+        if prediction_type not in ("sample", "epsilon"):
+            raise NotImplementedError(f"DDPMScheduler: prediction_type {prediction_type!r}")
+        if timestep_spacing not in ("leading", "linspace", "trailing"):
+            raise ValueError(timestep_spacing)
+        self.config = dict(num_train_timesteps=num_train_timesteps, beta_start=beta_start, beta_end=beta_end,
+                           beta_schedule=beta_schedule, variance_type=variance_type, clip_sample=False,
+                           prediction_type=prediction_type, thresholding=False, timestep_spacing=timestep_spacing,
+                           steps_offset=steps_offset)
+        self.num_train_timesteps = num_train_timesteps
+        self.prediction_type = prediction_type
+        self.alphas_cumprod = torch.cumprod(1.0 - _betas(beta_schedule, beta_start, beta_end, num_train_timesteps), dim=0)
+        self.timesteps = torch.arange(num_train_timesteps - 1, -1, -1)
+        self.num_inference_steps = None
+
+    @classmethod
+    def from_config(cls, config, **overrides):
+        c = _config_of(config, cls)
+        c.update(overrides)
+        return cls(**c)
+
+    @classmethod
+    def from_pretrained(cls, pretrained_model_name_or_path: str, subfolder: Optional[str] = None, **overrides):
+        """Reads ``<path>/<subfolder>/scheduler_config.json`` (the diffusers layout)."""
+        import json
+        import os
+
+        with open(os.path.join(pretrained_model_name_or_path, subfolder or "", "scheduler_config.json")) as f:
+            return cls.from_config(json.load(f), **overrides)
+
+    def set_timesteps(self, num_inference_steps: int, device=None):
+        import numpy as np
+
+        n_train, sp = self.num_train_timesteps, self.config["timestep_spacing"]
+        if num_inference_steps > n_train:
+            raise ValueError("num_inference_steps > num_train_timesteps")
+        if sp == "linspace":
+            ts = np.linspace(0, n_train - 1, num_inference_steps).round()[::-1].copy().astype(np.int64)
+        elif sp == "leading":
+            ts = (np.arange(0, num_inference_steps) * (n_train // num_inference_steps)).round()[::-1].copy().astype(np.int64)
+            ts += self.config["steps_offset"]
+        else:
+            ts = (np.round(np.arange(n_train, 0, -n_train / num_inference_steps)) - 1).astype(np.int64)
+        self.num_inference_steps = num_inference_steps
+        self.timesteps = torch.from_numpy(ts).to(device)
+
+    def scale_model_input(self, sample, timestep=None):
+        return sample
+
+    def _row64(self, t: int):
+        ac = self.alphas_cumprod
+        prev_t = t - self.num_train_timesteps // (self.num_inference_steps or self.num_train_timesteps)
+        a_t = float(ac[t])
+        a_prev = float(ac[prev_t]) if prev_t >= 0 else 1.0
+        cur_alpha = a_t / a_prev
+        cur_beta = 1 - cur_alpha
+        p1 = a_prev ** 0.5 * cur_beta / (1 - a_t)               # weight of the predicted x0 (eq. 7)
+        p0 = cur_alpha ** 0.5 * (1 - a_prev) / (1 - a_t)        # weight of the current sample
+        pn = 0.0
+        if t > 0:
+            var = max((1 - a_prev) / (1 - a_t) * cur_beta, 1e-20) if self.config["variance_type"] == "fixed_small" else cur_beta
+            pn = var ** 0.5
+        return (p0, p1, 0.0, pn)
+
+    def coefficient_table(self) -> torch.Tensor:
+        """[n, 4] fp32 rows (p0, p1, 0, pn) over ``timesteps`` for ``ur_sde_update``."""
+        return torch.tensor([self._row64(int(t)) for t in self.timesteps.cpu().tolist()], dtype=torch.float32).reshape(-1, 4)
+
+    def step(self, model_output: torch.Tensor, timestep, sample: torch.Tensor, generator=None,
+             variance_noise: Optional[torch.Tensor] = None, return_dict: bool = False, **_):
+        t = int(torch.as_tensor(timestep).flatten()[0].item())
+        m = model_output
+        if self.prediction_type == "epsilon":
+            cd = torch.float64 if sample.dtype == torch.float64 else torch.float32
+            a_t = float(self.alphas_cumprod[t])
+            m = (sample.to(cd) - (1 - a_t) ** 0.5 * model_output.to(cd)) / a_t ** 0.5
+        prev = _linear_step(self._row64(t), m, sample, None, generator, variance_noise)
+        return (prev,) if not return_dict else {"prev_sample": prev}
+
+    def add_noise(self, original, noise, timesteps):
+        a = self.alphas_cumprod.to(original.device)[timesteps.long()].to(original.dtype)
+        while a.dim() < original.dim():
+            a = a[..., None]
+        return a.sqrt() * original + (1 - a).sqrt() * noise
+
+
+class DPMSolverMultistepScheduler:
+    """DPM-Solver++ (Lu et al. 2022, arXiv 2211.01095: Algorithm 1 = first order, Algorithm 2 = 2M) and its SDE variant
+    (Sec. 5 / eq. 18 of the same paper's v2), restated from the published algorithms as diffusers 0.24's
+    ``DPMSolverMultistepScheduler`` parameterises them: data prediction, ``algorithm_type`` ``dpmsolver++`` /
+    ``sde-dpmsolver++``, ``solver_order`` 1 / 2 with ``solver_type="midpoint"``, first-order warm-up, ``lower_order_final``
+    (the last step of a loop of fewer than 15 steps is first order), ``use_karras_sigmas`` (Karras et al. 2022, rho = 7; the
+    last sigma is repeated as in 0.24, so the last step is the identity), ``timestep_spacing`` as UniPC has it.  diffusers is
+    not available here, so parity with it is unpinned; the class is pinned by properties
+    (tests/test_stochastic_samplers_cpu.py): order 1 == DDIM, order-2 convergence on the Gaussian flow, the marginal of an SDE
+    step under a perfect predictor, table == step arithmetic.
+
+    With lambda = log(alpha / sigma), h = lambda_t - lambda_s, r = (lambda_s - lambda_s') / h, m the newest and m' the previous
+    x0 prediction:
+        dpmsolver++       x_t = (sigma_t / sigma_s) x        + alpha_t (1 - e^-h)  [m + (m - m') / (2 r)]
+        sde-dpmsolver++   x_t = (sigma_t / sigma_s) e^-h x   + alpha_t (1 - e^-2h) [m + (m - m') / (2 r)] + sigma_t sqrt(1 - e^-2h) xi
+    (first order: without the bracket's second term).  The deterministic variant is the same recurrence with pn = 0.
+
+    NOT implemented (``NotImplementedError``): ``algorithm_type`` ``dpmsolver`` / ``sde-dpmsolver``, ``solver_order`` 3,
+    ``solver_type="heun"``, ``euler_at_final``, ``thresholding``, ``lambda_min_clipped``, the learned ``variance_type``s,
+    ``v_prediction``."""
+
+    init_noise_sigma = 1.0
+    order = 1
+
+    def __init__(self, num_train_timesteps: int = 1000, beta_start: float = 0.0001, beta_end: float = 0.02,
+                 beta_schedule: str = "linear", solver_order: int = 2, prediction_type: str = "epsilon",
+                 thresholding: bool = False, algorithm_type: str = "dpmsolver++", solver_type: str = "midpoint",
+                 lower_order_final: bool = True, euler_at_final: bool = False, use_karras_sigmas: bool = False,
+                 lambda_min_clipped: float = -float("inf"), variance_type=None, timestep_spacing: str = "linspace",
+                 steps_offset: int = 0, trained_betas=None, **_ignored):
+        if algorithm_type not in ("dpmsolver++", "sde-dpmsolver++"):
+            raise NotImplementedError(f"DPMSolverMultistepScheduler: algorithm_type {algorithm_type!r} "
+                                      "(dpmsolver++ / sde-dpmsolver++ are implemented)")
+        if solver_order not in (1, 2):
+            raise NotImplementedError("DPMSolverMultistepScheduler: solver_order 1 / 2 are implemented")
+        if solver_type != "midpoint":
+            raise NotImplementedError(f"DPMSolverMultistepScheduler: solver_type {solver_type!r} (midpoint is implemented)")
+        if euler_at_final or thresholding or variance_type is not None or trained_betas is not None \
+                or lambda_min_clipped != -float("inf"):
+            raise NotImplementedError("DPMSolverMultistepScheduler: euler_at_final, thresholding, learned variance types, "
+                                      "trained_betas and lambda_min_clipped are not implemented")
+        if prediction_type not in ("sample", "epsilon"):
+            raise NotImplementedError(f"DPMSolverMultistepScheduler: prediction_type {prediction_type!r}")
+        if timestep_spacing not in ("leading", "linspace", "trailing"):
+            raise ValueError(timestep_spacing)
+        self.config = dict(num_train_timesteps=num_train_timesteps, beta_start=beta_start, beta_end=beta_end,
+                           beta_schedule=beta_schedule, solver_order=solver_order, prediction_type=prediction_type,
+                           algorithm_type=algorithm_type, solver_type=solver_type, lower_order_final=lower_order_final,
+                           use_karras_sigmas=use_karras_sigmas, timestep_spacing=timestep_spacing, steps_offset=steps_offset)
+        self.num_train_timesteps = num_train_timesteps
+        self.prediction_type = prediction_type
+        self.solver_order = solver_order
+        self.alphas_cumprod = torch.cumprod(1.0 - _betas(beta_schedule, beta_start, beta_end, num_train_timesteps), dim=0)
+        self.timesteps = torch.arange(num_train_timesteps - 1, -1, -1)
+        self.num_inference_steps = None
+        self.sigmas = None
+        self._reset()
+
+    @classmethod
+    def from_config(cls, config, **overrides):
+        c = _config_of(config, cls)
+        for k in ("predict_x0", "disable_corrector"):  # a UniPC config names these; they have no meaning here
+            c.pop(k, None)
+        if isinstance(config, UniPCMultistepScheduler) or "solver_type" in c and c["solver_type"] in ("bh1", "bh2"):
+            c.pop("solver_type", None)
+        c.update(overrides)
+        return cls(**c)
+
+    def _reset(self):
+        self._m_prev = None
+        self._step_index = None
+
+    def set_timesteps(self, num_inference_steps: int, device=None):
+        import numpy as np
+
+        n_train, sp = self.num_train_timesteps, self.config["timestep_spacing"]
+        if sp == "linspace":
+            ts = np.linspace(0, n_train - 1, num_inference_steps + 1).round()[::-1][:-1].copy().astype(np.int64)
+        elif sp == "leading":
+            ratio = n_train // (num_inference_steps + 1)
+            ts = (np.arange(0, num_inference_steps + 1) * ratio).round()[::-1][:-1].copy().astype(np.int64)
+            ts += self.config["steps_offset"]
+        else:
+            ts = (np.arange(n_train, 0, -n_train / num_inference_steps).round() - 1).astype(np.int64)
+        ac = self.alphas_cumprod.numpy().astype(np.float64)
+        sig = ((1 - ac) / ac) ** 0.5
+        if self.config["use_karras_sigmas"]:
+            rho, ramp = 7.0, np.linspace(0, 1, num_inference_steps)
+            lo, hi = sig[0] ** (1 / rho), sig[-1] ** (1 / rho)
+            sigmas = (hi + ramp * (lo - hi)) ** rho
+            # the (fractional, then rounded) training timestep of each sigma: linear interpolation in log sigma
+            ts = np.interp(np.log(np.maximum(sigmas, 1e-10)), np.log(sig), np.arange(len(sig))).round().astype(np.int64)
+            sigmas = np.concatenate([sigmas, sigmas[-1:]])
+        else:
+            sigmas = np.concatenate([np.interp(ts, np.arange(0, len(sig)), sig), [sig[0]]])
+        self.sigmas = torch.from_numpy(sigmas.astype(np.float32))
+        self.timesteps = torch.from_numpy(ts).to(device=device, dtype=torch.int64)
+        self.num_inference_steps = len(ts)
+        self._reset()
+
+    def scale_model_input(self, sample, timestep=None):
+        return sample
+
+    @staticmethod
+    def _alpha_sigma(sigma):
+        alpha_t = 1.0 / ((sigma ** 2 + 1.0) ** 0.5)
+        return alpha_t, sigma * alpha_t
+
+    def _orders(self):
+        """The order of the update at every step index (first-order warm-up, lower_order_final)."""
+        n, out = self.num_inference_steps, []
+        for i in range(n):
+            final = i == n - 1 and self.config["lower_order_final"] and n < 15
+            out.append(1 if (self.solver_order == 1 or i < 1 or final) else 2)
+        return out
+
+    def _rows64(self):
+        import math
+
+        sde = self.config["algorithm_type"] == "sde-dpmsolver++"
+        sg = [float(s) for s in self.sigmas.double().tolist()]
+        lam = lambda s: -math.log(s)  # log(alpha / sigma_t) = -log(sigma) with alpha = 1 / sqrt(sigma^2 + 1), sigma_t = sigma alpha
+        rows = []
+        for i, o in enumerate(self._orders()):
+            a_t, s_t = self._alpha_sigma(sg[i + 1])
+            _, s_0 = self._alpha_sigma(sg[i])
+            h = lam(sg[i + 1]) - lam(sg[i])
+            if h == 0.0:  # the repeated last sigma of the Karras grid: the identity
+                rows.append((1.0, 0.0, 0.0, 0.0))
+                continue
+            if sde:
+                p0, d0, pn = s_t / s_0 * math.exp(-h), a_t * -math.expm1(-2.0 * h), s_t * (-math.expm1(-2.0 * h)) ** 0.5
+            else:
+                p0, d0, pn = s_t / s_0, a_t * -math.expm1(-h), 0.0
+            p1, p2 = d0, 0.0
+            if o == 2:
+                r = (lam(sg[i]) - lam(sg[i - 1])) / h
+                w = 0.5 * d0 / r  # weight of D1 = (m - m') / r
+                p1, p2 = d0 + w, -w
+            rows.append((p0, p1, p2, pn))
+        return rows
+
+    def coefficient_table(self) -> torch.Tensor:
+        """[n, 4] fp32 rows (p0, p1, p2, pn) for ``ur_sde_update``; pn = 0 throughout for ``dpmsolver++``."""
+        return torch.tensor(self._rows64(), dtype=torch.float32).reshape(-1, 4)
+
+    def _index_for(self, timestep):
+        t = int(torch.as_tensor(timestep).flatten()[0].item())
+        idx = (self.timesteps.cpu() == t).nonzero()
+        return int(idx[1 if len(idx) > 1 else 0]) if len(idx) else len(self.timesteps) - 1
+
+    def step(self, model_output: torch.Tensor, timestep, sample: torch.Tensor, generator=None,
+             variance_noise: Optional[torch.Tensor] = None, return_dict: bool = False, **_):
+        """One multistep update: the fp32 row of ``coefficient_table`` in the kernel's order, one rounding to
+        ``sample.dtype``; the previous x0 prediction is kept in the computation dtype."""
+        if self.num_inference_steps is None:
+            raise ValueError("DPMSolverMultistepScheduler.step: call set_timesteps first")
+        if self._step_index is None:
+            self._step_index = self._index_for(timestep)
+        i = min(self._step_index, self.num_inference_steps - 1)
+        cd = torch.float64 if sample.dtype == torch.float64 else torch.float32
+        m = model_output.to(cd)
+        if self.prediction_type == "epsilon":
+            a, s = self._alpha_sigma(float(self.sigmas[i]))
+            m = (sample.to(cd) - s * m) / a
+        prev = _linear_step(self._rows64()[i], m, sample, self._m_prev, generator, variance_noise)
+        self._m_prev = m
+        self._step_index += 1
+        return (prev,) if not return_dict else {"prev_sample": prev}
+
+    def add_noise(self, original, noise, timesteps):
+        a = self.alphas_cumprod.to(original.device)[timesteps.long()].to(original.dtype)
+        while a.dim() < original.dim():
+            a = a[..., None]
+        return a.sqrt() * original + (1 - a).sqrt() * noise
+
+
+def _refused(name: str, why: str):
+    def __init__(self, *a, **k):
+        raise NotImplementedError(f"{name}: {why}")
+
+    return type(name, (), {"__init__": __init__, "from_config": classmethod(lambda cls, *a, **k: cls()),
+                           "from_pretrained": classmethod(lambda cls, *a, **k: cls()),
+                           "__doc__": f"Not implemented: {why}"})
+
+
+_SIGMA_SPACE = ("works on sigma-scaled inputs (init_noise_sigma != 1, scale_model_input); the sampling loops here keep the "
+                "latents in the variance-preserving parameterisation.  DDIM, DDPM, DPM-Solver++ and UniPC are implemented")
+EulerDiscreteScheduler = _refused("EulerDiscreteScheduler", _SIGMA_SPACE)
+EulerAncestralDiscreteScheduler = _refused("EulerAncestralDiscreteScheduler", _SIGMA_SPACE)
+HeunDiscreteScheduler = _refused("HeunDiscreteScheduler", _SIGMA_SPACE)
+PNDMScheduler = _refused("PNDMScheduler", "the PNDM / PLMS family is not implemented.  DDIM, DDPM, DPM-Solver++ and UniPC are")
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# The noise of the stochastic samplers on the host: the stream ur_sde_update / ur_sampler_noise draw on the device, so
+# that CPU pipelines and CPU tests see the same numbers (to the fp32 accuracy of the device's log / sqrt / sin / cos).  It is
+# the package's own stream, NOT torch.randn's.
+# ---------------------------------------------------------------------------------------------------------------------
+def philox4x32_10(counter, key):
+    """Philox4x32-10 (Salmon et al., SC'11; Random123) in numpy ``uint64``: ``counter`` [..., 4] and ``key`` [..., 2] hold
+    32-bit words; returns the four output words [..., 4] as ``uint64``."""
+    import numpy as np
+
+    c = np.asarray(counter, dtype=np.uint64) & np.uint64(0xFFFFFFFF)
+    k = np.asarray(key, dtype=np.uint64) & np.uint64(0xFFFFFFFF)
+    c0, c1, c2, c3 = (c[..., j].copy() for j in range(4))
+    k0, k1 = k[..., 0].copy(), k[..., 1].copy()
+    M0, M1, W0, W1, MASK, S32 = (np.uint64(v) for v in (0xD2511F53, 0xCD9E8D57, 0x9E3779B9, 0xBB67AE85, 0xFFFFFFFF, 32))
+    for _ in range(10):
+        p0, p1 = M0 * c0, M1 * c2  # 32 x 32 -> 64 bits: exact in uint64
+        c0, c1, c2, c3 = (p1 >> S32) ^ c1 ^ k0, p1 & MASK, (p0 >> S32) ^ c3 ^ k1, p0 & MASK
+        k0, k1 = (k0 + W0) & MASK, (k1 + W1) & MASK
+    return np.stack(np.broadcast_arrays(c0, c1, c2, c3), axis=-1)
+
+
+def philox_normal(seed: int, step: int, shape) -> torch.Tensor:
+    """fp32 CPU tensor of ``shape``: the standard normals ``ur_sde_update`` draws at step ``step`` under ``seed`` for a latent
+    of that logical contiguous shape (include/ur_kernels.h: group g = e // 4, counter (g lo, g hi, step, 0), key (seed lo,
+    seed hi), u = ((w >> 8) + 0.5) 2^-24, Box-Muller on (w0, w1) and (w2, w3)), evaluated in float64."""
+    import numpy as np
+
+    n = 1
+    for d in shape:
+        n *= int(d)
+    seed, groups = int(seed) & 0xFFFFFFFFFFFFFFFF, (n + 3) // 4
+    g = np.arange(groups, dtype=np.uint64)
+    ctr = np.stack([g & np.uint64(0xFFFFFFFF), g >> np.uint64(32), np.full(groups, int(step), dtype=np.uint64),
+                    np.zeros(groups, dtype=np.uint64)], axis=-1)
+    w = philox4x32_10(ctr, np.array([seed & 0xFFFFFFFF, seed >> 32], dtype=np.uint64))
+    u = ((w >> np.uint64(8)).astype(np.float64) + 0.5) * 2.0 ** -24
+    r0, r1 = np.sqrt(-2.0 * np.log(u[:, 0])), np.sqrt(-2.0 * np.log(u[:, 2]))
+    t0, t1 = 2.0 * np.pi * u[:, 1], 2.0 * np.pi * u[:, 3]
+    z = np.stack([r0 * np.cos(t0), r0 * np.sin(t0), r1 * np.cos(t1), r1 * np.sin(t1)], axis=-1).reshape(-1)[:n]
+    return torch.from_numpy(z.astype(np.float32)).reshape(tuple(int(d) for d in shape))
