@@ -41,6 +41,8 @@
  *   ur_blend_tiles  the stitch of diffusers' AutoencoderKL.tiled_decode / tiled_encode behind enable_vae_tiling
  *                   (models/pipeline.py:200-215): blend_v / blend_h over the tile grid, the crops and the two torch.cat, as one
  *                   launch that also converts NHWC to NCHW.
+ *   ur_ema_advance / ur_ema_multi   diffusers' training_utils.EMAModel.step (the --use_ema switch of its training scripts): the
+ *                   decay schedule and `s_param.sub_(one_minus_decay * (s_param - param))` over all parameters.
  */
 #ifndef UR_KERNELS_H
 #define UR_KERNELS_H
@@ -56,7 +58,7 @@ extern "C" {
  * every ur_sizeof_X() against struct ur_X).  So it is written in the few shapes that reader accepts -- `#define UR_NAME
  * <integer>`; structs of pointers (to void / float / int / uint8_t / uint32_t / int32_t / int64_t), int32_t / int64_t / int / float and
  * char[N] fields; functions of int / int32_t / int64_t /
- * float and pointer parameters that return int, int64_t or const char* -- and no field is named like a Python keyword. */
+ * float and pointer (also to double) parameters that return int, int64_t or const char* -- and no field is named like a Python keyword. */
 #define UR_ABI_VERSION 17
 
 #define UR_E_BADARG (-1001)   /* inconsistent descriptor (shape / alignment / null pointer)   */
@@ -828,6 +830,38 @@ int ur_adam8_quantize(const float* x, uint8_t* codes, float* absmax, int64_t n, 
 int ur_adam8_dequantize(float* x, const uint8_t* codes, const float* absmax, int64_t n, int is_signed, void* stream);
 /* Host only: copies the 256 ascending fp32 entries of a code book into HOST memory out256. */
 int ur_adam8_codebook(int is_signed, float* out256);
+
+/* Exponential moving average of the weights (csrc/ema.hip; an ADDITION to ABI 17, nothing existing changes): the update of
+ * diffusers' training_utils.EMAModel.step, `s_param.sub_(one_minus_decay * (s_param - param))`, over many tensors per launch,
+ * with the decay schedule in device memory so that a captured training step advances it by itself.
+ *
+ * ur_ema_advance: a one-thread kernel.  *step += 1, then EMAModel.get_decay (diffusers 0.24, restated; parity unpinned) of
+ * the new step in fp64:
+ *     k = max(0, step - update_after_step - 1)
+ *     k <= 0: 0.0;   use_ema_warmup: 1 - (1 + k / inv_gamma) ** -power;   else (1 + k) / (10 + k)
+ *     then min(., decay), then max(., min_decay)            (k <= 0 stays 0.0: diffusers returns before the clamps)
+ * written to *cur_decay, and *one_minus_decay = (float)(1.0 - cur_decay).  step (int64), cur_decay (fp64) and one_minus_decay
+ * (fp32) are DEVICE scalars.  schedule: a HOST table of four doubles { inv_gamma, power, min_decay, decay }, passed on by
+ * value (the binding's reader knows no double parameters by value; tests/test_host_cpu.py pins that).  UR_E_BADARG: a null
+ * pointer, inv_gamma <= 0, a NaN, min_decay or decay outside [0, 1].
+ *
+ * ur_ema_multi: up to ur_ema_multi_max() (UR_EMA_MAX_TENSORS = 64; no #define: the constant census is pinned too) tensors per
+ * launch.  items: a HOST table of ur_ema_item_words() = 4 int64_t words per tensor, [n_tensors][4] = { shadow, param, n,
+ * flags }: float* shadow (fp32, always), the parameter's address, the element count, and flags = the parameter's dtype
+ * (UR_DT_F32 / UR_DT_F16 / UR_DT_BF16) in bits 0..7, | 0x100: COPY.  Per element, with d = *one_minus_decay read from DEVICE memory and p
+ * widened exactly to fp32: t = s - p, u = d * t, s = s - u -- three separately rounded fp32 operations, never contracted
+ * into an fma, and no shortcut for d == 0 or d == 1 (s - 1 * (s - p) is not p in fp32; diffusers takes none either).  COPY
+ * (what EMAModel does for requires_grad = False parameters): s = (float)p.  The parameter is never written.  Tensors whose
+ * two addresses are 16-byte aligned take 16-byte shadow accesses (and 16-byte / 8-byte parameter loads); others go element
+ * by element.  One workgroup owns ur_ema_block_elems() consecutive elements of one tensor.  Checks and return codes as
+ * ur_adamw8_multi: a null or element-misaligned address, n <= 0, an unknown dtype or flag bit in any row, n_tensors outside
+ * 1 .. ur_ema_multi_max(): UR_E_BADARG before any launch. */
+int ur_ema_advance(int64_t* step, int64_t update_after_step, int use_ema_warmup, const double* schedule, double* cur_decay,
+                   float* one_minus_decay, void* stream);
+int ur_ema_multi(const int64_t* items, int n_tensors, const float* one_minus_decay, void* stream);
+int ur_ema_multi_max(void);   /* host only */
+int ur_ema_item_words(void);  /* host only */
+int ur_ema_block_elems(void); /* host only */
 
 /* Flash backward of o = softmax(q k^T * scale) v (ur_attention_backward_supported: Tq % 64 == 0, d % 8 == 0, d <= 160).
  * Replaces the reference's autograd through F.scaled_dot_product_attention (diffusers AttnProcessor2_0 under

@@ -59,6 +59,9 @@ def main():
     ap.add_argument("--lora-targets", default="attn", choices=["attn", "attn+ff"], help="the adapted modules: the attention "
                     "projections, or those and the feed-forward matrices")
     ap.add_argument("--freeze-exchange-nets", action="store_true", help="with --lora-rank: freeze the encoder and the decoder too")
+    ap.add_argument("--ema", action="store_true", help="keep an exponential moving average of every network's weights "
+                    "(training_utils.EMAModel, diffusers' --use_ema): one EMAModel per network, stepped after the optimizer update, "
+                    "inside the graph with --graph")
     args = ap.parse_args()
     world, rank, local = (int(os.environ.get(k, d)) for k, d in (("WORLD_SIZE", "1"), ("RANK", "0"), ("LOCAL_RANK", "0")))
     if args.gpus > 1 and world == 1 and "RANK" not in os.environ:
@@ -108,10 +111,15 @@ def main():
         if (world > 1 or args.force_collectives) else None
     if buckets is not None and args.accumulate_into_buckets:
         buckets.direct_write = False
+    ema = None
+    if args.ema:
+        from uni_renderer_amd import EMAModel
+        ema = [EMAModel(m.parameters(), model_cls=type(m), model_config=m.config) for m in nets]
+    ema_kw = dict(ema=ema) if ema is not None else {}  # (without --ema the calls are the ones a tree without EMAModel takes)
     if args.graph:
         # one GPU: the whole step is one graph; several: forward + backward graph, eager bucket collectives and update
         from uni_renderer_amd.train_step import GraphedTrainStep
-        gstep = GraphedTrainStep(nets, batch, opt, buckets=buckets, dtype=dt)
+        gstep = GraphedTrainStep(nets, batch, opt, buckets=buckets, dtype=dt, **ema_kw)
         gstats = gstep.step()
         torch.cuda.synchronize()
         t0 = time.perf_counter()
@@ -125,11 +133,11 @@ def main():
         if gstep.capture_collectives:
             phases["collectives_forked_during_backward"] = gstep.collectives_from_hooks
     else:
-        stats = train_step(nets, batch, optimizer=opt, buckets=buckets, dtype=dt)  # warm-up (packs nothing: weights change)
+        stats = train_step(nets, batch, optimizer=opt, buckets=buckets, dtype=dt, **ema_kw)  # warm-up (packs nothing: weights change)
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         for _ in range(args.steps):
-            stats = train_step(nets, batch, optimizer=opt, buckets=buckets, dtype=dt)
+            stats = train_step(nets, batch, optimizer=opt, buckets=buckets, dtype=dt, **ema_kw)
         torch.cuda.synchronize()
         dtm = (time.perf_counter() - t0) / args.steps
     if world > 1:
@@ -146,6 +154,8 @@ def main():
                               lora=(dict(rank=args.lora_rank, targets=args.lora_targets, matrices=len(nets[0].lora_parameters()) // 2,
                                          frozen_exchange_nets=bool(args.freeze_exchange_nets)) if args.lora_rank else None),
                               trainable_params=sum(p.numel() for p in params),
+                              ema=(dict(models=len(ema), averaged_params=sum(s.numel() for e in ema for s in e.shadow_params),
+                                        optimization_step=ema[0].optimization_step) if ema is not None else None),
                               wgrad_queue=_queue_stats(), phase_ms=(phases if args.graph else None))))
     if world > 1 or args.force_collectives:
         torch.distributed.barrier()

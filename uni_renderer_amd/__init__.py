@@ -10,6 +10,7 @@ from .controlnet import (AttributeDecoderModel, AttributeEncoderModel, ControlNe
 from .optim import AdamW8bit, FusedAdamW
 from .pipeline import UniRendererPipeline
 from .schedulers import DDIMScheduler, DDPMScheduler, DPMSolverMultistepScheduler, UniPCMultistepScheduler
+from .training_utils import EMAModel
 from .vae import AutoencoderKL
 from .unet_2d_blocks import (CrossAttnDownBlock2D, CrossAttnUpBlock2D, CrossAttnUpResBlock2D, DownBlock2D,
                              UNetMidBlock2DCrossAttn, UpBlock2D, UpResBlock2D, get_down_block, get_up_block)
@@ -20,6 +21,6 @@ __all__ = [
     "CrossAttnDownBlock2D", "DownBlock2D", "UNetMidBlock2DCrossAttn", "UpBlock2D", "CrossAttnUpBlock2D",
     "UpResBlock2D", "CrossAttnUpResBlock2D", "get_down_block", "get_up_block",
     "UniRendererPipeline", "AutoencoderKL", "DDIMScheduler", "UniPCMultistepScheduler", "DDPMScheduler",
-    "DPMSolverMultistepScheduler", "FusedAdamW", "AdamW8bit",
+    "DPMSolverMultistepScheduler", "FusedAdamW", "AdamW8bit", "EMAModel",
 ]
 __version__ = "0.1.0"

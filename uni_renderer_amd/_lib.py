@@ -33,7 +33,7 @@ class UrLibraryError(RuntimeError):
 # ---------------------------------------------------------------------------------------------
 _SCALARS = {"int": C.c_int, "int32_t": C.c_int32, "int64_t": C.c_int64, "float": C.c_float}
 _TYPED_POINTEES = ("int32_t", "int64_t")                   # T* parameters that become POINTER(T): host-side out values / tables
-_OPAQUE_POINTEES = ("void", "float", "int", "uint32_t", "uint8_t")  # device memory (or a stream handle): c_void_p
+_OPAQUE_POINTEES = ("void", "float", "double", "int", "uint32_t", "uint8_t")  # device memory (or a stream handle): c_void_p
 _RETURNS = {"int": C.c_int, "int64_t": C.c_int64, "char*": C.c_char_p}
 _DECL = re.compile(r"(\w+)\s*((?:\*\s*)*)(\w*)")           # base type, stars, name -- `const` already removed
 _FIELD = re.compile(r"(\*?)\s*(\w+)(?:\s*\[\s*(\d+)\s*\])?")

@@ -20,6 +20,7 @@ import torch
 
 SUBFOLDERS = {"AttributeEncoderModel": "controlnet", "AttributeDecoderModel": "controldec", "UNet2DConditionModel": "unet"}
 OPTIMIZER_NAME = "optimizer.bin"
+EMA_SUFFIX = "_ema"
 PREFIX = "checkpoint"
 
 
@@ -49,10 +50,20 @@ def rotate_checkpoints(output_dir: str, checkpoints_total_limit: Optional[int]) 
     return removed
 
 
+def _ema_subfolder(ema) -> str:
+    """``unet_ema`` (the name diffusers' training scripts use), ``controlnet_ema``, ``controldec_ema``: by the class name of the
+    network the average belongs to, as the networks' own folders."""
+    name = getattr(getattr(ema, "model_cls", None), "__name__", None)
+    if name not in SUBFOLDERS:
+        raise ValueError(f"EMAModel of unknown network class {name}: build it with model_cls= one of {sorted(SUBFOLDERS)}")
+    return SUBFOLDERS[name] + EMA_SUFFIX
+
+
 def save_state(models: Sequence[torch.nn.Module], output_dir: str, global_step: int, optimizer=None,
-               checkpoints_total_limit: Optional[int] = None, is_main_process: bool = True) -> Optional[str]:
+               checkpoints_total_limit: Optional[int] = None, is_main_process: bool = True, ema_models=None) -> Optional[str]:
     """``output_dir/checkpoint-{global_step}/{controlnet,controldec,unet}/`` (+ ``optimizer.bin``), after rotation.
-    Only the main process writes (train.py:1433); every rank may call this."""
+    Only the main process writes (train.py:1433); every rank may call this.  ``ema_models``: ``training_utils.EMAModel``s, each
+    written with its ``save_pretrained`` to ``{controlnet,controldec,unet}_ema/``."""
     if not is_main_process:
         return None
     os.makedirs(output_dir, exist_ok=True)
@@ -64,15 +75,18 @@ def save_state(models: Sequence[torch.nn.Module], output_dir: str, global_step: 
         if sub is None:
             raise ValueError(f"unknown network class {m.__class__.__name__} (the reference's hooks match by class name)")
         m.save_pretrained(os.path.join(path, sub))
+    for ema in ema_models or ():
+        ema.save_pretrained(os.path.join(path, _ema_subfolder(ema)))
     if optimizer is not None:
         torch.save(optimizer.state_dict(), os.path.join(path, OPTIMIZER_NAME))
     return path
 
 
-def load_state(models: Sequence[torch.nn.Module], input_dir: str, optimizer=None) -> None:
+def load_state(models: Sequence[torch.nn.Module], input_dir: str, optimizer=None, ema_models=None) -> None:
     """The load hook of train.py:1022-1042: every network is re-read in diffusers layout from its sub-folder, its config
     is patched over the live module's (``register_to_config``) and the weights are loaded IN PLACE (the live modules
-    keep their identity, device and dtype: optimizers and DDP wrappers built over them stay valid)."""
+    keep their identity, device and dtype: optimizers and DDP wrappers built over them stay valid).  ``ema_models`` are read
+    back from their ``*_ema/`` folders IN PLACE too (``EMAModel.load_state_dict``: a captured training step stays valid)."""
     for m in models:
         m = _unwrap(m)
         sub = SUBFOLDERS.get(m.__class__.__name__)
@@ -82,13 +96,18 @@ def load_state(models: Sequence[torch.nn.Module], input_dir: str, optimizer=None
         m.register_to_config(**loaded.config)
         m.load_state_dict(loaded.state_dict())
         del loaded
+    for ema in ema_models or ():
+        loaded = type(ema).from_pretrained(os.path.join(input_dir, _ema_subfolder(ema)), ema.model_cls)
+        ema.load_state_dict(loaded.state_dict())
+        del loaded
     opt_path = os.path.join(input_dir, OPTIMIZER_NAME)
     if optimizer is not None and os.path.exists(opt_path):
         optimizer.load_state_dict(torch.load(opt_path, map_location="cpu"))
 
 
 def resume_from_checkpoint(models: Sequence[torch.nn.Module], output_dir: str, resume: Optional[str], optimizer=None,
-                           learning_rate: Optional[float] = None, betas: Optional[Tuple[float, float]] = None) -> int:
+                           learning_rate: Optional[float] = None, betas: Optional[Tuple[float, float]] = None,
+                           ema_models=None) -> int:
     """train.py:1191-1218.  ``resume``: ``None`` (fresh run), ``"latest"`` (largest ``checkpoint-N`` in ``output_dir``)
     or a checkpoint path / name (its basename is looked up in ``output_dir``, 1193).  Returns the global step to continue
     from (0 when nothing was loaded).  After loading, lr / betas of every param group are overwritten with the given
@@ -102,7 +121,7 @@ def resume_from_checkpoint(models: Sequence[torch.nn.Module], output_dir: str, r
         name = ckpts[-1] if ckpts else None
     if name is None or not os.path.isdir(os.path.join(output_dir, name)):
         return 0  # "Checkpoint ... does not exist. Starting a new training run." (1202-1206)
-    load_state(models, os.path.join(output_dir, name), optimizer)
+    load_state(models, os.path.join(output_dir, name), optimizer, ema_models=ema_models)
     if optimizer is not None:
         for g in optimizer.param_groups:
             if learning_rate is not None:

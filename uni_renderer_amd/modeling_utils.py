@@ -102,10 +102,16 @@ class ConfigModelMixin:
         save_file(sd, os.path.join(save_directory, WEIGHTS_NAME))
 
     @classmethod
-    def load_config(cls, path: str, subfolder: str = None, **_) -> Dict[str, Any]:
+    def load_config(cls, path: str, subfolder: str = None, return_unused_kwargs: bool = False, **_) -> Dict[str, Any]:
+        """``config.json`` as a dict.  ``return_unused_kwargs`` (diffusers' switch, what ``EMAModel.from_pretrained`` reads its
+        scalars with): ``(config, unused)`` instead, ``unused`` being the public entries that are no argument of ``__init__``."""
         p = os.path.join(path, subfolder) if subfolder else path
         with open(os.path.join(p, CONFIG_NAME)) as f:
-            return json.load(f)
+            config = json.load(f)
+        if not return_unused_kwargs:
+            return config
+        sig = inspect.signature(cls.__init__).parameters
+        return config, {k: v for k, v in config.items() if k not in sig and not k.startswith("_")}
 
     @classmethod
     def from_config(cls, config: Dict[str, Any], **overrides):

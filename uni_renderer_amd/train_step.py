@@ -556,11 +556,32 @@ def _parameters(nets) -> list:
     return hit[1]
 
 
-def _clip_and_update(nets, optimizer, buckets, max_grad_norm, stats, scaler=None):
+def _ema_list(nets, ema) -> list:
+    """``ema`` of train_step / GraphedTrainStep as [(EMAModel, the parameters it averages)]: one ``training_utils.EMAModel`` over
+    all parameters of ``nets`` in order, or a sequence with one entry (or None) per network, as the diffusers scripts keep one
+    ``ema_unet`` per model."""
+    if ema is None:
+        return []
+    if hasattr(ema, "shadow_params"):
+        return [(ema, _parameters(nets))]
+    ema = list(ema)
+    if len(ema) != len(nets):
+        raise ValueError(f"ema: {len(ema)} EMAModels for {len(nets)} networks (pass one per network, None to leave one out)")
+    return [(e, _parameters((n,))) for e, n in zip(ema, nets) if e is not None]
+
+
+def _clip_and_update(nets, optimizer, buckets, max_grad_norm, stats, scaler=None, ema=None):
     """train.py:1422-1425: clip_grad_norm_ + optimizer.step(), the clipping folded into the optimizer pass when it can.
     With ``scaler`` (fp16 AMP, train.sh:21): the reference's order -- ``unscale_`` (which also looks for inf / nan),
     clip, ``scaler.step`` (skips the update when an overflow was found: parameters, moments and the step counter stay),
-    ``scaler.update``."""
+    ``scaler.update``.  ``ema``: the averages step after the update (also after one the scaler skipped, as in the diffusers
+    scripts)."""
+    _update(nets, optimizer, buckets, max_grad_norm, stats, scaler)
+    for e, params in _ema_list(nets, ema):
+        e.step(params)
+
+
+def _update(nets, optimizer, buckets, max_grad_norm, stats, scaler):
     if scaler is not None:
         if optimizer is None:
             raise ValueError("a GradScaler needs the optimizer whose gradients it unscales")
@@ -620,7 +641,7 @@ def _clip_and_update(nets, optimizer, buckets, max_grad_norm, stats, scaler=None
 
 def train_step(nets: Sequence[torch.nn.Module], batch: Dict[str, torch.Tensor], optimizer=None, buckets=None,
                dtype=torch.bfloat16, max_grad_norm: Optional[float] = 1.0, inverse: Optional[bool] = None,
-               as_tensors: bool = False, grad_accum: Optional[tuple] = None, scaler=None) -> Dict[str, float]:
+               as_tensors: bool = False, grad_accum: Optional[tuple] = None, scaler=None, ema=None) -> Dict[str, float]:
     """One optimisation step: forward, losses, backward (HIP kernels), gradient all-reduce (``buckets``: a
     parallel.GradientBuckets, no-op on one rank), clipping (train.py:1422-1424), optimizer step.
     ``grad_accum`` = (k, n): micro-step k of n (``accelerator.accumulate``, train.py:1236): gradients are zeroed at
@@ -630,7 +651,12 @@ def train_step(nets: Sequence[torch.nn.Module], batch: Dict[str, torch.Tensor], 
     (cycle consistency) / rendering (contrastive) objectives (reference_losses).  Ranks may pick different branches
     (compute_t, train.py:445): parameters without a gradient contribute zeros to the buckets.
     ``as_tensors``: return the statistics as device tensors (no host synchronisation: the step can then be captured
-    into a HIP graph, tools/train_bench.py --graph)."""
+    into a HIP graph, tools/train_bench.py --graph).
+    ``ema``: a ``training_utils.EMAModel`` over all parameters of ``nets``, or a sequence of them, one per network (None to
+    leave one out): each takes its ``step()`` after the optimizer update (diffusers' ``--use_ema``)."""
+    if ema is not None and optimizer is None:
+        raise ValueError("ema needs the optimizer whose update it follows")
+    _ema_list(nets, ema)  # a wrong count raises before anything ran
     stats = {"loss": _forward_backward(nets, batch, optimizer, buckets, dtype, inverse, grad_accum=grad_accum, scaler=scaler)}
     last = grad_accum is None or grad_accum[0] + 1 == grad_accum[1]
     if buckets is not None:
@@ -640,7 +666,7 @@ def train_step(nets: Sequence[torch.nn.Module], batch: Dict[str, torch.Tensor], 
             with buckets.no_sync():
                 buckets.finish()  # an accumulation micro-step: only adopts gradients re-created outside the buckets
     if last:
-        _clip_and_update(nets, optimizer, buckets, max_grad_norm, stats, scaler=scaler)
+        _clip_and_update(nets, optimizer, buckets, max_grad_norm, stats, scaler=scaler, ema=ema)
     return stats if as_tensors else {k: float(v) for k, v in stats.items()}
 
 
@@ -662,8 +688,12 @@ class GraphedTrainStep:
 
     def __init__(self, nets, batch: Dict[str, torch.Tensor], optimizer, buckets=None, dtype=torch.bfloat16,
                  max_grad_norm: Optional[float] = 1.0, inverse: Optional[bool] = None, warmup: int = 2,
-                 capture_collectives: Optional[bool] = None):
-        """``capture_collectives`` (RCCL only; default: on when ``buckets`` were built with ``overlap=True`` on the nccl
+                 capture_collectives: Optional[bool] = None, ema=None):
+        """``ema``: as in ``train_step``.  The averages step in the warm-up steps (they are real optimisation steps) and INSIDE
+        the captured graph, behind the optimizer update (without buckets the one graph, with them the update graph): their
+        decay schedule lives in device memory, so every replay advances it by itself.
+
+        ``capture_collectives`` (RCCL only; default: on when ``buckets`` were built with ``overlap=True`` on the nccl
         backend): the bucket collectives are captured INTO the step graph.  The post-accumulate hooks of ``buckets`` enqueue
         each bucket's all-reduce / reduce-scatter + all-gather on RCCL's stream the moment the bucket is complete -- inside a
         capture that is a fork: the collective becomes a parallel branch of the graph that runs beside the rest of the
@@ -687,7 +717,8 @@ class GraphedTrainStep:
             t = torch.zeros(8, device=buckets.flat[0].device)
             dist.all_reduce(t, group=buckets.group)
             torch.cuda.synchronize()
-        self.nets, self.optimizer, self.buckets = nets, optimizer, buckets
+        self.nets, self.optimizer, self.buckets, self.ema = nets, optimizer, buckets, ema
+        _ema_list(nets, ema)  # a wrong count raises before anything ran
         # gloo (the CPU-side test transport) stages device tensors through the host; handing it a tensor whose producer
         # graph is still replaying was measured at 50-140 s per step with two ranks on one GPU (0.03 s after a stream
         # synchronise).  RCCL collectives are stream-ordered and need no host wait.
@@ -715,6 +746,7 @@ class GraphedTrainStep:
         self.max_grad_norm = max_grad_norm
         self._kw = kw
         self._updated = [p for grp in optimizer.param_groups for p in grp["params"] if p.requires_grad]
+        self._updated += [s for e, _ in _ema_list(nets, ema) for s in e.shadow_params]  # written by the captured step too
         self._capture()
 
     def _hyper(self):
@@ -724,7 +756,7 @@ class GraphedTrainStep:
         dev_lr = hasattr(self.optimizer, "sync_hyper")
         # ... and the ADDRESSES it holds: the device (lr, weight_decay) pair and the optimizer's ``generation`` (bumped when
         # load_state_dict / add_param_group replaced state tensors a captured update points at)
-        return (getattr(self.optimizer, "generation", 0),) + tuple(
+        return (getattr(self.optimizer, "generation", 0),) + tuple(e.generation for e, _ in _ema_list(self.nets, self.ema)) + tuple(
             ((None if dev_lr else float(g["lr"])), tuple(float(b) for b in g["betas"]), float(g["eps"]),
              (None if dev_lr else float(g["weight_decay"])),
              (g["_ur_hyper"][0].data_ptr() if g.get("_ur_hyper") is not None else None)) for g in self.optimizer.param_groups)
@@ -746,13 +778,13 @@ class GraphedTrainStep:
                 self.stats["loss"] = _forward_backward(nets, self.batch, None, buckets, **kw)
                 self.collectives_from_hooks = buckets.launched_from_hooks - before  # forked before finish() had to
                 buckets.finish()  # launches what the hooks could not, then joins RCCL's stream (work.wait = stream wait)
-                _clip_and_update(nets, optimizer, buckets, max_grad_norm, self.stats)
+                _clip_and_update(nets, optimizer, buckets, max_grad_norm, self.stats, ema=self.ema)
             self._validate_captured_collectives()
             return
         with torch.cuda.graph(self.g_fb):
             self.stats["loss"] = _forward_backward(nets, self.batch, optimizer if buckets is None else None, buckets, **kw)
             if buckets is None:
-                _clip_and_update(nets, optimizer, None, max_grad_norm, self.stats)
+                _clip_and_update(nets, optimizer, None, max_grad_norm, self.stats, ema=self.ema)
         if buckets is not None:
             buckets._reset()
             # the eager finish() before every replay leaves the clipping norm's sums of squares in fixed buffers when the
@@ -761,7 +793,7 @@ class GraphedTrainStep:
             buckets.sumsq_parts = buckets.sumsq_buffers() if buckets.fused_sumsq() else None
             self.g_up = torch.cuda.CUDAGraph()
             with torch.cuda.graph(self.g_up):
-                _clip_and_update(nets, optimizer, buckets, max_grad_norm, self.stats)
+                _clip_and_update(nets, optimizer, buckets, max_grad_norm, self.stats, ema=self.ema)
             buckets.sumsq_parts = None
 
     def _validate_captured_collectives(self):
@@ -799,7 +831,7 @@ class GraphedTrainStep:
         st = {"loss": _forward_backward(self.nets, self.batch, self.optimizer, self.buckets, **kw)}
         if self.buckets is not None:
             self.buckets.finish()
-        _clip_and_update(self.nets, self.optimizer, self.buckets, max_grad_norm, st)
+        _clip_and_update(self.nets, self.optimizer, self.buckets, max_grad_norm, st, ema=self.ema)
 
     def step(self, batch: Optional[Dict[str, torch.Tensor]] = None) -> Dict[str, torch.Tensor]:
         """One optimisation step on ``batch`` (copied into the captured input buffers; None: the last one again).
