@@ -730,7 +730,11 @@ int ur_transpose2d_multi(const ur_transpose_desc* descs, int n, int dtype, void*
  *   N % 8 == 0, K % 8 == 0 (taps == 9: C % 64 == 0, K = 9 * C, Hout and Wout powers of two); P arbitrary.
  *   splits > 1: the P range is cut into `splits` slices (each a multiple of 32 rows), fp32 slabs in `partial`
  *   (ur_wgrad_plan gives the slice count the library would choose and the floats needed), summed in slice order by a
- *   second launch -- deterministic.  db may be NULL.  dw is written in `dtype`.
+ *   second launch -- deterministic.  db may be NULL.  dw is written in `dtype`.  splits may not exceed the number of
+ *   32-row stages, ceil(P / 32) (UR_E_BADARG); below that, trailing slices without work are legal and write zero slabs.
+ *   lddw >= K (a multiple of 4), taps == 9: ldx >= C (a multiple of 8) and pad 1 or 0 -- pad 0 puts the whole padding
+ *   behind the last line / column (F.pad(x, (0, 1, 0, 1)) + padding 0); all of these are tested per element
+ *   (tests/test_wgrad_range_gpu.py).
  */
 typedef struct ur_wgrad_desc {
     const void* dy;       /* [P][lddy]                                                              */

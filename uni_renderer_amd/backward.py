@@ -589,6 +589,14 @@ def _pad_rows64(t: torch.Tensor) -> torch.Tensor:
     return out
 
 
+def _dx_linear(dy2: torch.Tensor, wt: torch.Tensor) -> torch.Tensor:
+    """dx = dy2 @ wt^T for dy2 [M, N] and wt [K, ceil8(N)] (``transpose2d`` of the weight).  ``ops.linear`` reads compact rows
+    and ``ur_igemm`` contracts in 64-wide chunks: a row-strided dy2 (a column slice of a wider gradient) is copied, and an N
+    that is no multiple of 64 is zero-padded on both operands.  Neither costs anything for the layers of the UNet (compact
+    gradients, N a multiple of 64)."""
+    return ops.linear(_pad_cols64(dy2), _pad_rows64(wt))
+
+
 def linear_backward(x: torch.Tensor, w: torch.Tensor, dy: torch.Tensor, need_bias: bool = True, defer: bool = False,
                     need_dw: bool = True) -> Tuple[torch.Tensor, Optional[torch.Tensor], Optional[torch.Tensor]]:
     """y = x @ w^T + b  (x [..., K], w [N, K] in the compute dtype, dy [..., N])  ->  (dx, dw, db).
@@ -598,21 +606,23 @@ def linear_backward(x: torch.Tensor, w: torch.Tensor, dy: torch.Tensor, need_bia
     x2, dy2 = x.reshape(-1, K), dy.reshape(-1, N)
     if not need_dw:
         wt = weight_t.lookup((w.data_ptr(), tuple(w.shape)))
-        dx = ops.linear(dy2, wt if wt is not None else transpose2d(w)).view(x.shape)
+        dx = _dx_linear(dy2, wt if wt is not None else transpose2d(w)).view(x.shape)
         return dx, None, (colsum(dy2.contiguous()) if need_bias else None)
     if WGRAD and wgrad_ok(dy2, x2):
         wt = weight_t.lookup((w.data_ptr(), tuple(w.shape)))
-        dx = ops.linear(dy2, wt if wt is not None else transpose2d(w)).view(x.shape)   # [M, N] @ [K, N]^T
+        dx = _dx_linear(dy2, wt if wt is not None else transpose2d(w)).view(x.shape)   # [M, N] @ [K, N]^T
         later = wgrad_queue.add(dy2, x2, w, need_bias) if (defer and WGRAD_DEFER) else None
         dw, db = later if later is not None else wgrad(dy2, x2, need_bias)
         return dx, dw, db
-    dy2p = dy2  # transpose2d zero-pads the row count (M = batch rows in the time-embedding GEMMs) to a multiple of 8
+    # transpose2d zero-pads the row count (M = batch rows in the time-embedding GEMMs) to a multiple of 8; ur_colsum reads
+    # compact rows (a column slice of a wider gradient is copied)
+    dy2p = dy2.contiguous()
     # [K, N], [N, Mp], [K, Mp]: one launch; the last two zero-padded to the 64-granularity of the dW contraction
     if need_bias:
         (wt, dyt, xt), db = transpose2d_many([w, dy2p, x2], colsum_of=1, pad64=(1, 2))
     else:
         (wt, dyt, xt), db = transpose2d_many([w, dy2p, x2], pad64=(1, 2)), None
-    dx = ops.linear(dy2, wt).view(x.shape)                # [M, N] @ [K, N]^T
+    dx = _dx_linear(dy2p, wt).view(x.shape)               # [M, N] @ [K, N]^T
     dw = ops.linear(dyt, xt)                              # [N, M] @ [K, M]^T = [N, K]
     wgrad_stats["problems"] += 1
     return dx, dw, db
