@@ -38,6 +38,9 @@
  *                   (models/unet_2d_blocks.py:2343-2370, 2522-2546, 2653-2677, 2767-2790): the in-place backbone scale
  *                   `hidden[:, : C // 2] *= b` and fourier_filter's fftn -> fftshift -> box * s -> ifftshift -> ifftn -> real
  *                   of the skip, as one launch without an FFT.
+ *   ur_ip_attention_add   the image half of diffusers' IPAdapterAttnProcessor2_0 behind every cross-attention of the UNet (the
+ *                   reference's pipeline derives from IPAdapterMixin, models/pipeline.py:11,125; models/controlnet.py:1009-1016):
+ *                   to_k_ip / to_v_ip head reshapes, F.scaled_dot_product_attention over the image tokens, `scale *` and the add.
  *   ur_blend_tiles  the stitch of diffusers' AutoencoderKL.tiled_decode / tiled_encode behind enable_vae_tiling
  *                   (models/pipeline.py:200-215): blend_v / blend_h over the tile grid, the crops and the two torch.cat, as one
  *                   launch that also converts NHWC to NCHW.
@@ -378,6 +381,34 @@ int ur_add_hilo(const void* a, const void* a_lo, const void* b, const void* b_lo
  */
 int ur_freeu(void* hidden, void* hidden_lo, int Ch, float b, const void* skip, const void* skip_lo, void* skip_out,
              void* skip_out_lo, int Cs, float s, int B, int H, int W, int dtype, void* stream);
+
+/*
+ * ur_ip_attention_add (csrc/ipadapter.hip; an ADDITION to ABI 17, nothing existing changes): the image half of IP-Adapter's
+ * decoupled cross-attention (arXiv 2308.06721), added IN PLACE to the output o of the prompt's ur_attention:
+ *     o[b][t][h*d .. +d] += scale * sum_j p_j * v_ip[b][j][h*d .. +d],   p = softmax over j of q[b][t][h] . k_ip[b][j][h]
+ * for B samples, T query tokens, H heads of width d and N image tokens -- a second softmax with its own normaliser.
+ *   o     [B][T][H*d], contiguous.
+ *   q     exactly what the cross-attention's ur_attention launch received: q_hstride == 0: token-major [B][T][ldq], head h at
+ *         columns q_off + h*d; q_hstride > 0: the head-major image (ur_attn_desc above; sample b at q + q_off + b * T * ldq,
+ *         head h a further h * q_hstride on, rows d apart).  q carries d^-1/2 * log2(e): the scores are in log2 units and the
+ *         softmax is an exp2.  qk_scale <= 0 says so (pass 0); qk_scale > 0 ("scale the scores, natural exp") is
+ *         UR_E_UNSUPPORTED.
+ *   k_ip, v_ip   image keys / values in `dtype`: token j of sample b at + (b * N + j) * ldkv, head h at columns h*d (ldkv >= H*d:
+ *         [B][N][H*d], or column slices of a wider batched projection).
+ * d in {32, 40, 64, 80, 128, 160} (8 heads of 40 / 80 / 160 are the SD-1.x UNet's; the power-of-two widths serve small test
+ * networks), H * d <= 1280, 1 <= N <= 16, otherwise UR_E_UNSUPPORTED.  UR_E_BADARG: a null or not 16-byte aligned pointer,
+ * sizes <= 0, ldq / q_off / q_hstride / ldkv not multiples of 8, q_off + H*d > ldq (token-major), a head-major image that
+ * does not fit its sample, ldkv < H*d, a non-finite scale, unknown flags or dtype.  scale == 0 launches nothing.
+ * fp32 scores, max-subtracted exp2, sum and weighted sum in a fixed order without atomics (bit-reproducible); the one rounding
+ * to `dtype` is that of o + scale * ip.  q is read once, o read once and written once, in 16-byte vectors; a sample's k_ip /
+ * v_ip (4 N H d bytes, at most 80 KB) are staged once per workgroup.  flags: 0 in the executors; bit 0 (value 1) = the
+ * one-thread-per-(token, head) kernel instead of the one-lane-per-vector one; bits 8 .. 15: 0, or the number of pair groups a
+ * workgroup walks instead of the launcher's choice (both for A/B runs and tests: every combination gives the same bits); any
+ * other bit is UR_E_BADARG.
+ */
+int ur_ip_attention_add(void* o, const void* q, const void* k_ip, const void* v_ip, float scale, float qk_scale, int B, int H,
+                        int T, int d, int N, int64_t ldq, int q_off, int64_t q_hstride, int64_t ldkv, int flags, int dtype,
+                        void* stream);
 
 /*
  * Direct 3x3 convolution, pad 1, stride 1 | 2, for maps with FEW channels (csrc/condconv.hip): the seven narrow layers of the

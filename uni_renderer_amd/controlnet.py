@@ -12,7 +12,8 @@ caller are zero-copy NCHW *views* (channels-last strides) of those NHWC buffers,
 back without a copy -- the 13+13 exchange tensors never change layout between the three networks.
 
 Configuration branches that the SD-1.x checkpoint family leaves inactive (class / addition embeddings,
-encoder_hid_proj, GLIGEN, attention masks) raise ``NotImplementedError``, and so does every key of
+encoder_hid_proj other than a loaded IP-Adapter's -- ``ip_adapter.py``: ``added_cond_kwargs={"image_embeds": ...}`` is taken by a
+UNet with an adapter and refused otherwise --, GLIGEN, attention masks) raise ``NotImplementedError``, and so does every key of
 ``cross_attention_kwargs`` other than ``scale``.  ``cross_attention_kwargs={"scale": s}`` is the LoRA scale: the UNet merges
 its adapters at ``s`` before the call (``lora.py``); the other three networks have no adapters and ignore it.
 """
@@ -27,6 +28,7 @@ import torch
 import torch.nn as nn
 
 from . import ops
+from .ip_adapter import IP_AUTOGRAD_MSG, UNetIPAdapterMixin, image_embeds_msg
 from .lora import UNetLoraMixin, scale_of
 from . import packs as R
 from .layers import Attention, ControlNetConditioningEmbedding, Conv2d, Ctx, GroupNorm, PackCache, ResnetBlock2D, \
@@ -218,7 +220,7 @@ def _exchange_channels(block_out_channels, layers_per_block):
 
 
 # =====================================================================================================
-class UNet2DConditionModel(UNetLoraMixin, _DenoiserBase):
+class UNet2DConditionModel(UNetIPAdapterMixin, UNetLoraMixin, _DenoiserBase):
     """Image stream.  ``forward(..., return_dict=False)`` returns
     ``(sample, raw_down_block_res_samples[12], raw_mid_block_sample, up_block_res_samples[13])`` (ref 1163-1164)."""
 
@@ -370,11 +372,21 @@ class UNet2DConditionModel(UNetLoraMixin, _DenoiserBase):
         return_dict: bool = True,
     ):
         _reject_inactive(class_labels=class_labels, timestep_cond=timestep_cond, attention_mask=attention_mask,
-                         added_cond_kwargs=added_cond_kwargs,
                          down_intrablock_additional_residuals=down_intrablock_additional_residuals,
                          encoder_attention_mask=encoder_attention_mask)
+        if self._ip is None:
+            _reject_inactive(added_cond_kwargs=added_cond_kwargs)
         lora_scale = scale_of(cross_attention_kwargs)
         autograd = self._autograd_mode(sample, encoder_hidden_states, down_block_additional_residuals, mid_block_additional_residual)
+        if self._ip is not None:  # ref 1009-1016: the image prompt of an IP-Adapter (encoder_hid_dim_type == "ip_image_proj")
+            if autograd:
+                raise NotImplementedError(IP_AUTOGRAD_MSG)
+            if added_cond_kwargs is None or "image_embeds" not in added_cond_kwargs:
+                raise ValueError(image_embeds_msg(self.__class__))
+            other = [k for k in added_cond_kwargs if k != "image_embeds"]
+            if other:
+                raise NotImplementedError(f"added_cond_kwargs[{other[0]!r}] is not supported on the MI355X hot path")
+            self.set_ip_adapter_image_embeds(added_cond_kwargs["image_embeds"])
         if self._lora is not None and not autograd:
             self._lora_apply(lora_scale)  # re-merges only when the scale or a trainable factor differs from what was merged
         if autograd:
@@ -409,6 +421,7 @@ class UNet2DConditionModel(UNetLoraMixin, _DenoiserBase):
     def forward_down_mid(self, sample, timestep, encoder_hidden_states):
         B, _, H, W = sample.shape
         ctx = self._begin(B, timestep, sample.device, encoder_hidden_states)
+        ctx.ip = self.ip_context(B, ctx.dtype)  # image K | V of an IP-Adapter, from the static embedding buffer
         x = self._conv_in(sample, ctx)
         skips = (x,)
         for blk in self.down_blocks:

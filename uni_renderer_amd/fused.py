@@ -74,6 +74,8 @@ class GroupedDualStreamStep:
         self.side_level = X.number("side_stream", 0)
         self.use_side = self.side_level != 0
         self._side = None
+        # ip_adapter.IpContext of the call in flight: the image K | V of a UNet with an IP-Adapter (None: no adapter, scale 0)
+        self._ipc = None
 
     # ------------------------------------------------------------------ second stream (graph branch)
     class _Fork:
@@ -197,10 +199,25 @@ class GroupedDualStreamStep:
             lo, hi = kv_slice
             o = ops.attention(q, kc[:, :, lo:hi], vtc[:, lo:hi], B=Bt, H=H, Tq=T, Tk=kc.shape[1], d=d, ldq=C,
                               ldk=kc.stride(1), scale=0.0)
+            self._ip_add(as_, o, q, T)
         ops.set_site("co" if a0.is_cross else "ao")
         y = ops.linear(o, wo, bo, res=residual, streams=S, hilo=self.hilo)
         ops.set_site(None)
         return y
+
+    def _ip_add(self, as_: Sequence[Attention], o, q, T, q_hstride=0):
+        """IP-Adapter's decoupled cross-attention behind the prompt attention of the grouped cross-attentions ``as_``: one
+        ``ur_ip_attention_add`` launch over the sample rows of each network that has an adapter (the UNet's rows of the
+        [enc ; unet] / [unet ; dec] groups); ``q`` / ``q_hstride`` as the attention launch received them."""
+        ipc = self._ipc
+        if ipc is None:
+            return
+        Bn = o.shape[0] // len(as_)
+        for i, a in enumerate(as_):
+            kv = ipc.of(a)
+            if kv is not None:
+                ops.ip_attention_add(o, q, kv[0], kv[1], ipc.scale, B=o.shape[0], H=a.heads, T=T, d=a.dim_head, ldq=a.inner,
+                                     q_hstride=q_hstride, rows=(i * Bn, (i + 1) * Bn))
 
     def _tblock(self, bs: Sequence[BasicTransformerBlock], x, kc, vtc, kv_slice):
         S, pk, dt = len(bs), self.pk, x.dtype
@@ -250,6 +267,7 @@ class GroupedDualStreamStep:
         lo, hi = kv_slice
         o2 = ops.attention(q2.view(Bt, T, C), kc[:, :, lo:hi], vtc[:, lo:hi], B=Bt, H=H, Tq=T, Tk=kc.shape[1], d=d, ldq=C,
                            ldk=kc.stride(1), scale=0.0, q_hstride=T * d if hm else 0)
+        self._ip_add([b.attn2 for b in bs], o2, q2.view(Bt, T, C), T, q_hstride=T * d if hm else 0)
 
         wsf, csf = stacked(pk, R.chain_ff, ts, dt)
         out = tchain.chain_ff(o2.view(Bt * T, C), y1, ops.view_hilo(blk_in, Bt * T, C), wsf, csf, bs[0].norm3.eps, streams=S)
@@ -453,6 +471,7 @@ class GroupedDualStreamStep:
         dev = x_t.device
         B, _, H, W = x_t.shape
         ehs = self._prep_ehs(ehs, B, dt)
+        self._ipc = unet.ip_context(B, dt)  # an IP-Adapter's image K | V of all 16 cross-attentions: one small GEMM chain
         tvec = lambda t: self._tvec(t, B, dev)
 
         # --- time embeddings of the three networks in one grouped chain: rows [enc | unet | dec]

@@ -37,10 +37,12 @@ def dual_stream_step(unet, enc, dec, x_t, cond, ehs, t_img, t_attr, run_decoder:
         # through ``forward``: the caller sets the LoRA scale (``UniRendererPipeline`` does, once per sampling call, before it
         # takes the weights signature), and handing the merged scale back keeps ``forward`` from re-merging at its default
         merged = getattr(unet, "lora_scale", None)
+        # ... and an IP-Adapter's image embeddings are the ones the caller put into the UNet's static buffer
         img_pred, raw_unet, raw_mid_unet, _ = unet(
             x_t, t_img, encoder_hidden_states=ehs, down_block_additional_residuals=res,
             mid_block_additional_residual=mid, return_dict=False,
-            cross_attention_kwargs=None if merged is None else {"scale": merged})
+            cross_attention_kwargs=None if merged is None else {"scale": merged},
+            added_cond_kwargs=unet.ip_added_cond_kwargs(x_t.shape[0]))
         out = {"img_pred": img_pred}
         if run_decoder:
             out["attr_pred"] = dec(sample=raw_mid_enc, down_block_res_samples=raw_enc, timestep=t_attr,
@@ -79,7 +81,9 @@ class GraphedDualStreamStep:
     """Capture once, replay many times.  ``step(...)`` copies new inputs into the static buffers (device to
     device, on the replay stream) and launches the graph; the returned tensors are overwritten by the next call.
     The UNet's FreeU factors (``enable_freeu`` / ``disable_freeu``) are kernel arguments baked into the capture: a direct user
-    must ``capture()`` again after toggling them (``UniRendererPipeline`` keys its graphs on them)."""
+    must ``capture()`` again after toggling them (``UniRendererPipeline`` keys its graphs on them).  The same holds for an
+    IP-Adapter (``ip_adapter_state()``: loaded or not, its scale); its image embeddings are read from the UNet's static buffer
+    (``set_ip_adapter_image_embeds``), so new embeddings need no capture."""
 
     def __init__(self, unet, enc, dec, batch: int, latent_hw, cross_dim: int, dtype=torch.float16,
                  device="cuda", run_decoder: bool = True, cond_channels: int = 28, img_channels: int = 4,

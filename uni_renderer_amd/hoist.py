@@ -103,6 +103,8 @@ class HoistedSamplingStep:
         tv = g._tvec(t_fixed, B, x_fixed.device)
         inv = self.inv
         inv["ehs"], inv["B"], inv["dt"] = ehs, B, dt
+        # an IP-Adapter's image K | V depend on the image embeddings only: once per call, together with the prompt's
+        g._ipc = inv["ip"] = unet.ip_context(B, dt)
         if self.direction == "inverse":
             # the UNet's raw skips (captured before any residual is added: controlnet.py:1075, 1112)
             raw, _ = self._run_down_mid(unet, x_fixed, CIN_PAD, tv, ehs, B, dt)
@@ -154,6 +156,7 @@ class HoistedSamplingStep:
         tables of ``time_tables`` (one small launch) instead of recomputing them from ``t_var``."""
         g, inv = self.g, self.inv
         ehs, B, dt = inv["ehs"], inv["B"], inv["dt"]
+        g._ipc = inv.get("ip")
         if self.direction == "inverse":
             first, last = self.enc, self.dec
         else:

@@ -122,7 +122,7 @@ from .packs import PackCache, one  # noqa: E402,F401 -- PackCache is imported fr
 class Ctx:
     """Per-forward context handed down the module tree."""
 
-    __slots__ = ("dtype", "temb", "ehs", "B", "kc", "vtc")
+    __slots__ = ("dtype", "temb", "ehs", "B", "kc", "vtc", "ip")
 
     def __init__(self, dtype, B):
         self.dtype = dtype
@@ -131,6 +131,7 @@ class Ctx:
         self.ehs = None   # [B, 77, cross_dim] tokens in compute dtype
         self.kc = None    # [B, 77, sum(C)]   to_k(ehs) of every cross-attention of the network, one GEMM
         self.vtc = None   # [B, sum(C), 128]  to_v(ehs)^T of every cross-attention, one GEMM
+        self.ip = None    # ip_adapter.IpContext: image K | V of every cross-attention of a UNet with an IP-Adapter, one GEMM
 
 
 # ---------------------------------------------------------------------------------------------------
@@ -230,6 +231,7 @@ class Attention(nn.Module):
             q = ops.linear(xn, wq, out_scale=cs)
             o = ops.attention(q, ctx.kc[:, :, lo:hi], ctx.vtc[:, lo:hi], B=B, H=H, Tq=T, Tk=ctx.kc.shape[1], d=d,
                               ldq=C, ldk=ctx.kc.stride(1), scale=0.0)
+            self._ip_add(o, q, ctx, B, T)
             return ops.linear(o, wo, bo, res=residual, hilo=ops.PRECISE_RESIDUAL)
         wv = one(pk, R.matrix, self.to_v, dt)
         if not self.is_cross:
@@ -246,7 +248,15 @@ class Attention(nn.Module):
             k = ops.linear(ehs, wk)                        # [B,Tk,C]
             vt = ops.vt_proj(ehs, wv)                      # [B,C,ceil64(Tk)]
             o = ops.attention(q, k, vt, B=B, H=H, Tq=T, Tk=Tk, d=d, ldq=C, ldk=C, scale=0.0)
+            self._ip_add(o, q, ctx, B, T)
         return ops.linear(o, wo, bo, res=residual, hilo=ops.PRECISE_RESIDUAL)
+
+    def _ip_add(self, o, q, ctx: Ctx, B, T):
+        """IP-Adapter's decoupled cross-attention: ``o += scale * softmax(q k_ip^T) v_ip`` over the image tokens, one launch
+        behind the prompt's attention (``ctx.ip``: only a UNet with an adapter loaded has one)."""
+        kv = ctx.ip.of(self) if ctx.ip is not None else None
+        if kv is not None:
+            ops.ip_attention_add(o, q, kv[0], kv[1], ctx.ip.scale, B=B, H=self.heads, T=T, d=self.dim_head, ldq=self.inner)
 
 
 class GEGLU(nn.Module):

@@ -1047,6 +1047,51 @@ def freeu(hidden, skip, b: float, s: float, *, out=None, rows=None):
     return out
 
 
+IPA_THREAD_PER_HEAD, IPA_WALK_SHIFT = 1, 8  # ur_ip_attention_add's `flags` (include/ur_kernels.h): A/B runs and tests
+IPA_MAX_TOKENS = 16
+
+
+def ip_attention_add(o, q, k_ip, v_ip, scale: float, *, B, H, T, d, ldq, q_off=0, q_hstride=0, rows=None, flags=0):
+    """The image half of IP-Adapter's decoupled cross-attention, added IN PLACE to ``o`` (``ur_ip_attention_add``), one launch:
+    ``o[b, t, h*d:(h+1)*d] += scale * softmax_j(q[b, t, h] . k_ip[b, j, h]) @ v_ip[b, :, h*d:(h+1)*d]`` over the N image tokens.
+    ``o`` = the contiguous [B, T, H*d] output of the prompt's ``attention``; ``q`` / ``ldq`` / ``q_off`` / ``q_hstride`` exactly
+    what that launch received (``q`` carries d**-0.5 * log2(e): scores in log2 units); ``k_ip`` / ``v_ip`` [B, N, H*d], or
+    column slices of one wider [B, N, *] projection (last stride 1, a common row stride), N <= 16.  ``rows = (r0, r1)``: act on
+    samples ``[r0, r1)`` of ``o`` and ``q`` only (the rows of one network of a grouped launch); ``k_ip`` / ``v_ip`` then hold
+    the ``r1 - r0`` samples of that range.  ``scale == 0`` launches nothing.  ``flags``: ``IPA_THREAD_PER_HEAD`` = the alternative thread mapping, ``n << IPA_WALK_SHIFT`` = n pair groups per
+    workgroup instead of the launcher's choice (A/B runs, tests; same bits).  Returns ``o``."""
+    _require_gpu(o)
+    lib = _lib.load()
+    r0, r1 = (0, B) if rows is None else rows
+    if not 0 <= r0 < r1 <= B:
+        raise ValueError(f"ip_attention_add: rows {rows} outside the batch of {B}")
+    Cc = H * d
+    if o.dim() != 3 or tuple(o.shape) != (B, T, Cc) or not o.is_contiguous() or o.dtype not in DT:
+        raise ValueError("ip_attention_add: o is a contiguous fp16 / bf16 [B, T, H * d] tensor")
+    for t in (k_ip, v_ip):
+        if (t.dim() != 3 or t.shape[0] != r1 - r0 or t.shape[2] != Cc or t.shape != k_ip.shape or t.dtype != o.dtype or t.stride(2) != 1
+                or t.stride() != k_ip.stride() or t.stride(0) != t.shape[1] * t.stride(1)):
+            raise ValueError("ip_attention_add: k_ip / v_ip are [B, N, H * d] tensors (or column slices of one [B, N, *] projection) "
+                             "of o's dtype, B = the samples of `rows`")
+    N = k_ip.shape[1]
+    if not 1 <= N <= IPA_MAX_TOKENS:
+        raise ValueError(f"ip_attention_add: {N} image tokens; 1 .. {IPA_MAX_TOKENS} are supported")
+    if q.dtype != o.dtype or q.shape[0] != B or q.numel() < B * T * ldq:
+        raise ValueError("ip_attention_add: q holds B samples of T * ldq elements in o's dtype")
+    if not math.isfinite(scale):
+        raise ValueError("ip_attention_add: scale is not finite")
+    if scale == 0:
+        return o
+    es = o.element_size()
+    e0 = _prof_begin()
+    check(lib.ur_ip_attention_add(o.data_ptr() + r0 * T * Cc * es, q.data_ptr() + r0 * T * ldq * es,
+                                  k_ip.data_ptr(), v_ip.data_ptr(),
+                                  float(scale), 0.0, r1 - r0, H, T, d, N, int(ldq), int(q_off), int(q_hstride), k_ip.stride(1),
+                                  int(flags), DT[o.dtype], _stream()), "ur_ip_attention_add")
+    _prof_end(e0, f"ip_attention_d{d}", 4.0 * (r1 - r0) * T * N * Cc, (3.0 * T + 2.0 * N) * (r1 - r0) * Cc * es)
+    return o
+
+
 _AddItem = _lib.STRUCTS["ur_add_item"]
 ADD_MULTI_MAX = ABI.UR_ADD_MULTI_MAX
 

@@ -25,6 +25,7 @@ import torch
 
 from .controlnet import AttributeDecoderModel, AttributeEncoderModel, UNet2DConditionModel
 from . import ops
+from .ip_adapter import read_ip_adapter_file
 from .lora import read_lora_file, scale_of
 from .graph import GraphedDualStreamStep, GraphedHoistedStep, dual_stream_step
 from .schedulers import DDIMScheduler, retrieve_timesteps
@@ -103,6 +104,63 @@ class UniRendererPipeline:
         """ref 762-764."""
         self.unet.disable_freeu()
 
+    # ---- IP-Adapter image prompts (the reference's IPAdapterMixin, ref 11,125) ------------------------------
+    def load_ip_adapter(self, pretrained_model_name_or_path_or_dict, subfolder: Optional[str] = None,
+                        weight_name: Optional[str] = None, **kwargs):
+        """Loads an IP-Adapter (arXiv 2308.06721) into the UNet: a state dict in the original layout (``image_proj.*``,
+        ``ip_adapter.{id}.to_{k,v}_ip.weight``; flat or nested), a local ``.safetensors`` / ``.bin`` file, or a directory holding
+        ``[subfolder/]weight_name``.  Nothing is loaded from a hub.  Every sampling call then needs ``ip_adapter_image=`` and the
+        pipeline an ``image_encoder`` (a CLIP vision tower with projection, supplied by the caller like the text encoder).  Only
+        the UNet is adapted; the attribute encoder / decoder keep their prompt-only attention."""
+        if getattr(self, "unet", None) is None:
+            raise ValueError("The pipeline must have `unet` for using an IP-Adapter.")
+        self.unet._load_ip_adapter_weights(read_ip_adapter_file(pretrained_model_name_or_path_or_dict, subfolder, weight_name))
+
+    def set_ip_adapter_scale(self, scale: float):
+        """The image prompt's weight in every cross-attention of the UNet.  A kernel argument of the captured step, so it is
+        part of the graph key: graphs captured at another scale are never replayed."""
+        self.unet.set_ip_adapter_scale(scale)
+
+    def unload_ip_adapter(self):
+        """Drops the adapter; the pipeline behaves exactly as before ``load_ip_adapter``."""
+        self.unet.unload_ip_adapter()
+
+    def encode_image(self, image, device, num_images_per_prompt):
+        """ref 433-444: PIL / array through ``feature_extractor`` (a pixel tensor as it is), the CLIP image embedding of
+        ``image_encoder``, repeated per prompt; returns ``(image_embeds, zeros_like)``."""
+        dtype = next(self.image_encoder.parameters()).dtype
+        if not isinstance(image, torch.Tensor):
+            image = self.feature_extractor(image, return_tensors="pt").pixel_values
+        image = image.to(device=device, dtype=dtype)
+        image_embeds = self.image_encoder(image).image_embeds
+        image_embeds = image_embeds.repeat_interleave(num_images_per_prompt, dim=0)
+        return image_embeds, torch.zeros_like(image_embeds)
+
+    def _prepare_ip_adapter(self, ip_adapter_image, device, total: int, num_images_per_prompt: int):
+        """Puts the image prompt of a sampling call into the UNet's static embedding buffer: ``total`` rows, under
+        classifier-free guidance ``[zeros ; embeds]`` in the order of ``_batch_prompt``."""
+        loaded = self.unet.ip_adapter_state() is not None
+        if ip_adapter_image is None:
+            if loaded:
+                raise ValueError("an IP-Adapter is loaded: pass ip_adapter_image=, or unload_ip_adapter() first")
+            return
+        if not loaded:
+            raise ValueError("ip_adapter_image was passed but no IP-Adapter is loaded (load_ip_adapter first)")
+        if self.image_encoder is None:
+            raise ValueError("ip_adapter_image needs an image_encoder (the CLIP vision tower is not part of this package: pass "
+                             "image_encoder= to the pipeline)")
+        if not isinstance(ip_adapter_image, torch.Tensor) and self.feature_extractor is None:
+            raise ValueError("ip_adapter_image as a PIL image / array needs a feature_extractor; pass a pixel tensor otherwise")
+        embeds, uncond = self.encode_image(ip_adapter_image, device, num_images_per_prompt)
+        if embeds.shape[0] != total:
+            if total % embeds.shape[0]:
+                raise ValueError(f"{embeds.shape[0]} image embeddings for a batch of {total}")
+            embeds = embeds.repeat(total // embeds.shape[0], 1)
+            uncond = torch.zeros_like(embeds)
+        if self.do_classifier_free_guidance:
+            embeds = torch.cat([uncond, embeds])
+        self.unet.set_ip_adapter_image_embeds(embeds)
+
     # ---- VAE slicing / tiling (ref 185-215): the VAE's own switches ---------------------------------------
     def enable_vae_slicing(self):
         """The VAE encodes / decodes a batch one sample at a time (ref 185-190)."""
@@ -147,7 +205,8 @@ class UniRendererPipeline:
         """(device, (data_ptr, version) of every parameter) of the three networks: in-place updates bump ``_version``,
         re-assignments change ``data_ptr``.  ~1.7 k parameters: evaluated once per sampling call, not per step."""
         nets = [m for m in (self.unet, self.controlnet, self.controldec) if m is not None]
-        return (str(self.device),) + tuple((p_.data_ptr(), p_._version) for m in nets for p_ in m.parameters())
+        # ... and the identity and scale of the UNet's IP-Adapter, whose tensors are no parameters
+        return (str(self.device), self.unet.ip_adapter_state()) + tuple((p_.data_ptr(), p_._version) for m in nets for p_ in m.parameters())
 
     @property
     def device(self):
@@ -360,11 +419,12 @@ class UniRendererPipeline:
         return torch.stack(rows), torch.tensor(ts, dtype=torch.float32)
 
     def _graph_key(self, x_img, ehs, run_decoder, cond_scale: float = 1.0):
-        """Everything a captured step bakes in besides the weights: shapes, dtype, executor, conditioning scale and the
-        UNet's FreeU factors (kernel arguments of ``ur_freeu``)."""
+        """Everything a captured step bakes in besides the weights: shapes, dtype, executor, conditioning scale, the
+        UNet's FreeU factors (kernel arguments of ``ur_freeu``) and its IP-Adapter (identity, token count, scale: launches and
+        kernel arguments of ``ur_ip_attention_add``)."""
         B, _, h, w = x_img.shape
         return (str(x_img.device), B, h, w, ehs.shape[1], ehs.shape[2], run_decoder, self.unet.dtype, float(cond_scale),
-                self.hoist_invariants, self.rerun_invariants, freeu_state(self.unet))
+                self.hoist_invariants, self.rerun_invariants, freeu_state(self.unet), self.unet.ip_adapter_state())
 
     def _graph_for(self, x_img, cond28, ehs, run_decoder, cond_scale: float = 1.0, sig=None):
         """The captured step for these shapes / this conditioning scale, re-captured when the weights it baked in have
@@ -520,7 +580,10 @@ class UniRendererPipeline:
         returns the six latents instead of decoded images.  ``eta`` is DDIM's (other schedulers ignore it, as in the
         reference's ``prepare_extra_step_kwargs``).  A sampler with a noise term (DDIM with eta != 0, DDPM, SDE-DPM-Solver++)
         draws ONE int64 from ``generator`` per call and takes all its noise from the package's own counter-based stream
-        keyed by it (``_draw_seed``) -- reproducible under ``manual_seed``, not ``torch.randn``'s numbers."""
+        keyed by it (``_draw_seed``) -- reproducible under ``manual_seed``, not ``torch.randn``'s numbers.
+        ``ip_adapter_image`` (PIL / array through ``feature_extractor``, or a pixel tensor): the image prompt of a loaded
+        IP-Adapter (``load_ip_adapter``), encoded by ``image_encoder`` and folded with ``num_images_per_prompt``; it goes to
+        the UNet only, under classifier-free guidance as ``[zeros ; embeds]``."""
         self._guidance_scale = guidance_scale
         self.unet._lora_apply(scale_of(cross_attention_kwargs))  # before any _weights_signature(): graphs see merged weights
         device = self._execution_device
@@ -556,6 +619,7 @@ class UniRendererPipeline:
             image_latents = image_latents.repeat_interleave(num_images_per_prompt, dim=0)
             mask_latents = mask_latents.repeat_interleave(num_images_per_prompt, dim=0)
         prompt_embeds = self._batch_prompt(prompt_embeds, negative_prompt_embeds, total)
+        self._prepare_ip_adapter(ip_adapter_image, device, total, num_images_per_prompt)
         h8, w8 = image_latents.shape[-2:]
         height, width = height or h8 * self.vae_scale_factor, width or w8 * self.vae_scale_factor
         nlat = self.unet.config.in_channels
@@ -631,11 +695,11 @@ class UniRendererPipeline:
         negative_prompt=None, num_images_per_prompt: Optional[int] = 1, eta: float = 0.0, generator=None, latents=None,
         prompt_embeds=None, negative_prompt_embeds=None, output_type: Optional[str] = "pil", return_dict: bool = True,
         cross_attention_kwargs=None, controlnet_conditioning_scale: float = 1.0, guess_mode: bool = False,
-        attr_latents: Optional[torch.Tensor] = None, **kwargs,
+        attr_latents: Optional[torch.Tensor] = None, ip_adapter_image=None, **kwargs,
     ):
         """Rendering: attributes -> image (enc + unet per step; the decoder is not run, ref 1631-1639).
         ``attr_latents`` ([B,28,h,w], mask first) bypasses the VAE encodes of the seven attribute images.  ``eta`` /
-        ``generator``: as in ``real_image2mask_3mod_albedo``."""
+        ``generator`` / ``ip_adapter_image``: as in ``real_image2mask_3mod_albedo``."""
         self._guidance_scale = guidance_scale
         self.unet._lora_apply(scale_of(cross_attention_kwargs))  # before any _weights_signature(): graphs see merged weights
         device = self._execution_device
@@ -660,6 +724,7 @@ class UniRendererPipeline:
             attr_latents = torch.cat(parts, dim=1)
         batch_size = attr_latents.shape[0]
         prompt_embeds = self._batch_prompt(prompt_embeds, negative_prompt_embeds, batch_size)
+        self._prepare_ip_adapter(ip_adapter_image, device, batch_size, num_images_per_prompt)
         h8, w8 = attr_latents.shape[-2:]
         height, width = height or h8 * self.vae_scale_factor, width or w8 * self.vae_scale_factor
         latents_img = self.prepare_latents(batch_size, 4, height, width, prompt_embeds.dtype, device, generator, latents)

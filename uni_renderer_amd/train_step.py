@@ -389,6 +389,10 @@ def unet_forward(unet, x_nhwc, ehs, t_img, dt, res=None, mid_res=None, collect_u
     """UNet2DConditionModel (controlnet.py:781-1166).  ``x_nhwc`` [B,H,W,CIN_PAD]; ``res`` / ``mid_res``: the encoder's
     residuals (NHWC) or None.  Returns (img_pred, raw_down[12], raw_mid, up_res[13] | None), NHWC.
     ``lora_scale``: the scale of a trainable LoRA adapter (``cross_attention_kwargs["scale"]``; None: 1.0, or the pinned one)."""
+    if getattr(unet, "_ip", None) is not None:
+        from .ip_adapter import IP_AUTOGRAD_MSG
+
+        raise NotImplementedError(IP_AUTOGRAD_MSG)  # this path has neither the forward nor a backward of the image attention
     plan = None
     if getattr(unet, "_lora", None) is not None:
         if torch.is_grad_enabled():
