@@ -46,6 +46,8 @@
  *                   launch that also converts NHWC to NCHW.
  *   ur_ema_advance / ur_ema_multi   diffusers' training_utils.EMAModel.step (the --use_ema switch of its training scripts): the
  *                   decay schedule and `s_param.sub_(one_minus_decay * (s_param - param))` over all parameters.
+ *   ur_view_blend   MultiDiffusion (arXiv 2302.08113; diffusers' StableDiffusionPanoramaPipeline, not part of the reference): the
+ *                   `value / count` average of overlapping latent windows between two denoise steps and the re-cut of the windows.
  */
 #ifndef UR_KERNELS_H
 #define UR_KERNELS_H
@@ -663,6 +665,33 @@ int ur_sde_update(const void* pred, int pred_ld, int pred_c0, void* lat, int64_t
                   const float* coef, const int* step, int nsteps, const int64_t* seed, float* master, float* hist,
                   int round_master, int cfg, float guidance, int cfg_channels, int dtype, void* stream);
 int ur_sampler_noise(const int64_t* seed, int step, float* out, int64_t n, void* stream);
+
+/*
+ * ur_view_blend (csrc/multidiff.hip; an ADDITION to ABI 17, nothing existing changes): the per-step average of MultiDiffusion's
+ * overlapping views (arXiv 2302.08113; diffusers' StableDiffusionPanoramaPipeline: `value[window] += view; count[window] += 1`
+ * over the views, `latents = value / count`, the views cut out of `latents` again), restated from the paper and from that
+ * pipeline -- parity with diffusers is unpinned.  One in-place launch behind ur_ddim_update / ur_unipc_update / ur_sde_update.
+ * Geometry: rows x cols windows of wh x ww latent pixels, window (r, c) at (r * sy, c * sx), over H x W =
+ * ((rows - 1) * sy + wh) x ((cols - 1) * sx + ww); V = rows * cols; view v = r * cols + c of sample n is batch row n * V + v.
+ *   master  fp32 [N * V][C][wh][ww], contiguous: read, then overwritten with the blended values
+ *   lat     the network's input slice over the same samples, conventions as ur_ddim_update: channel planes contiguous, batch
+ *           stride lat_bstride (elements) free, dtype fp16 / bf16 / fp32 (UR_DT_F32 is accepted); `halves` (1, or 2 under
+ *           classifier-free guidance) copies of the N * V samples, copy h at batch row h * N * V + b; written, never read.
+ *           May be null: master and global only.
+ *   global  fp32 [N][C][H][W], contiguous: written
+ * Per global element: s = 0; over the covering views in ASCENDING v, s = s + master entry (fp32, in that order, no
+ * contraction); g = s / (float)count, correctly rounded; with round_master g is rounded once to lat's dtype (and widened).  g
+ * is stored to global, to every covering master entry and, rounded once to lat's dtype, to every covering lat entry of every
+ * half.  Race-free in place: one thread owns a global element, touches only the entries that map to it, and every entry maps
+ * to exactly one element.  Bytes outside those entries (other channels of lat's buffer, other samples) are not touched.
+ * UR_E_BADARG: a null master / global, a size <= 0, halves outside {1, 2}, lat_bstride < C * wh * ww, an unknown dtype, a
+ * stride above the window along an axis with several windows (uncovered pixels), H * W or N * V of 2^31 or more.
+ * UR_E_UNSUPPORTED: more than ur_view_blend_max_cover() (64: window 64 at stride 8) views covering one pixel,
+ * min(rows, ceil(wh / sy)) * min(cols, ceil(ww / sx)).  Both before any launch.
+ */
+int ur_view_blend(float* master, void* lat, int64_t lat_bstride, float* global, int N, int C, int rows, int cols, int wh, int ww,
+                  int sy, int sx, int halves, int round_master, int dtype, void* stream);
+int ur_view_blend_max_cover(void); /* host only */
 
 /*
  * Weight prefetch into the 256 MB Infinity Cache (MI355X's memory-side last-level cache).  One denoise step reads

@@ -958,6 +958,59 @@ def sampler_noise(seed, step: int, shape, out=None):
     return out
 
 
+def view_blend_max_cover() -> int:
+    """Covering views per pixel ``ur_view_blend`` takes (the library's ``ur_view_blend_max_cover``)."""
+    return int(_lib.load().ur_view_blend_max_cover())
+
+
+def view_blend(master, lat, global_out, geometry, halves: int = 1, round_master: bool = False):
+    """In-place MultiDiffusion blend of the views ``master`` (contiguous fp32 [N * V, C, wh, ww]; include/ur_kernels.h
+    ``ur_view_blend``): every pixel of the global latent becomes the mean of the views that cover it, summed in ascending view
+    index and divided once; the mean goes to ``global_out`` (contiguous fp32 [N, C, H, W]), back to every covering entry of
+    ``master`` and, rounded to its dtype, to every covering entry of ``lat`` -- the network's input slice [halves * N * V, C,
+    wh, ww] (batch stride free, channel planes contiguous, fp16 / bf16 / fp32; ``halves = 2``: cond + uncond copies under
+    guidance; None: no such slice).  ``geometry``: a ``multidiffusion.ViewGeometry`` (rows, cols, wh, ww, sy, sx).
+    ``round_master``: the mean is rounded through ``lat``'s dtype first, as the update kernels do.  Tensors on the CPU take
+    ``multidiffusion.blend_views_reference`` (the same bits)."""
+    from .multidiffusion import ViewGeometry, blend_views_reference
+
+    geo = geometry if isinstance(geometry, ViewGeometry) else ViewGeometry(*(int(v) for v in geometry))
+    V = geo.num_views
+    if master.dim() != 4 or master.dtype != torch.float32 or not master.is_contiguous() or master.shape[0] % V \
+            or tuple(master.shape[2:]) != (geo.wh, geo.ww):
+        raise RuntimeError(f"view_blend: master must be a contiguous fp32 [N * {V}, C, {geo.wh}, {geo.ww}] tensor")
+    NV, Cc = master.shape[0], master.shape[1]
+    N = NV // V
+    if halves not in (1, 2):
+        raise RuntimeError("view_blend: halves is 1, or 2 under classifier-free guidance")
+    if global_out.dtype != torch.float32 or not global_out.is_contiguous() or global_out.device != master.device \
+            or tuple(global_out.shape) != (N, Cc, geo.height, geo.width):
+        raise RuntimeError(f"view_blend: global_out must be a contiguous fp32 {(N, Cc, geo.height, geo.width)} tensor")
+    if lat is not None:
+        if lat.dtype not in DT_ANY or lat.device != master.device or tuple(lat.shape) != (halves * NV, Cc, geo.wh, geo.ww):
+            raise RuntimeError(f"view_blend: lat must be [{halves} * {NV}, {Cc}, {geo.wh}, {geo.ww}] in fp16 / bf16 / fp32")
+        if lat.stride(3) != 1 or lat.stride(2) != geo.ww or lat.stride(1) != geo.wh * geo.ww:
+            raise RuntimeError("view_blend: latent slice must have contiguous channel planes")
+    if (geo.rows > 1 and geo.sy > geo.wh) or (geo.cols > 1 and geo.sx > geo.ww) or min(geo) < 1:
+        raise RuntimeError("view_blend: bad geometry (a stride above the window leaves pixels uncovered)")
+    if not master.is_cuda:
+        dt = lat.dtype if lat is not None else torch.float32
+        views, glob = blend_views_reference(master, geo, return_global=True)
+        if round_master:
+            views, glob = views.to(dt).float(), glob.to(dt).float()
+        master.copy_(views)
+        global_out.copy_(glob)
+        if lat is not None:
+            lat.copy_(torch.cat([views] * halves).to(dt))
+        return
+    lib = _lib.load()
+    if geo.max_cover > view_blend_max_cover():
+        raise NotImplementedError(f"view_blend: {geo.max_cover} views cover one pixel; at most {view_blend_max_cover()} are supported")
+    check(lib.ur_view_blend(master.data_ptr(), _ptr(lat), lat.stride(0) if lat is not None else 0, global_out.data_ptr(), N, Cc,
+                            geo.rows, geo.cols, geo.wh, geo.ww, geo.sy, geo.sx, int(halves), int(round_master),
+                            DT_ANY[lat.dtype if lat is not None else torch.float32], _stream()), "ur_view_blend")
+
+
 def sampler_advance(step, tsteps, nsteps: int, t_out=None):
     lib = _lib.load()
     check(lib.ur_sampler_advance(step.data_ptr(), tsteps.data_ptr(), nsteps, _ptr(t_out),

@@ -26,6 +26,7 @@ import torch
 from .controlnet import AttributeDecoderModel, AttributeEncoderModel, UNet2DConditionModel
 from . import ops
 from .ip_adapter import read_ip_adapter_file
+from .multidiffusion import ViewGeometry, gather_views, view_geometry
 from .lora import read_lora_file, scale_of
 from .graph import GraphedDualStreamStep, GraphedHoistedStep, dual_stream_step
 from .schedulers import DDIMScheduler, retrieve_timesteps
@@ -60,6 +61,7 @@ class UniRendererPipeline:
         self._progress_kwargs: Dict[str, Any] = {}
         self._guidance_scale = 0.0
         self._num_timesteps = 0
+        self._multidiffusion: Optional[Dict[str, Any]] = None  # enable_multidiffusion: window_size, stride, view_batch_size
 
     # ---- construction / placement ---------------------------------------------------------------
     @classmethod
@@ -104,6 +106,71 @@ class UniRendererPipeline:
         """ref 762-764."""
         self.unet.disable_freeu()
 
+    # ---- MultiDiffusion views for latents larger than the training size ------------------------------------------
+    def enable_multidiffusion(self, window_size: int = 64, stride: int = 8, view_batch_size: Optional[int] = None):
+        """MultiDiffusion (arXiv 2302.08113; diffusers' ``StableDiffusionPanoramaPipeline``; restated from both, parity with
+        diffusers unpinned) for ``real_image2mask_3mod_albedo``, ``image2mask_3mod_albedo`` and ``mask2image_3mod_albedo``: a
+        latent larger than ``window_size`` (on either axis; sizes in LATENT pixels, 64 = the 512 x 512 images the networks
+        were trained on) is covered by overlapping square windows at every ``stride`` pixels, every window ("view") is
+        denoised as an ordinary sample of the batch, and after every sampler step the views are averaged where they overlap
+        (``ops.view_blend``, one launch inside the captured loop).  The inputs are encoded and the noise drawn at full size;
+        ``latents=`` / ``image_latents=`` / ``mask_latents=`` / ``attr_latents=`` are global tensors, cut into views once per
+        call; the prompt and image-prompt embeddings are repeated per view; the results are global.
+
+        Every view is its own batch element, so it has its own multistep history (UniPC's corrected sample, the previous
+        predictions) -- what diffusers does when it saves and restores the scheduler state per view.  A sampler with a noise
+        term keeps its ONE stream over the ``[N * V, ...]`` view batch: overlapping views get independent noise, as in diffusers.
+
+        The latent must be ``window_size + k * stride`` long on every axis longer than the window (``ValueError`` names the
+        nearest sizes), and at most 64 views may cover a pixel (window 64 with stride 8; ``NotImplementedError`` beyond).
+        ``view_batch_size``: the step-by-step loop runs the networks over at most that many views at a time (memory); the
+        on-device loop always takes all views as one batch.  A latent not larger than the window, or ``disable_multidiffusion``,
+        is today's path bit for bit: no launch, no graph key changes.
+
+        Not supported: circular padding (panoramas that wrap), different prompts or weights per view, non-square windows,
+        folding the blend into the update kernels, training."""
+        window_size, stride = int(window_size), int(stride)
+        if window_size < 1 or stride < 1:
+            raise ValueError("enable_multidiffusion: window_size and stride are positive numbers of latent pixels")
+        if view_batch_size is not None and int(view_batch_size) < 1:
+            raise ValueError("enable_multidiffusion: view_batch_size is None or >= 1")
+        self._multidiffusion = dict(window_size=window_size, stride=stride,
+                                    view_batch_size=None if view_batch_size is None else int(view_batch_size))
+
+    def disable_multidiffusion(self):
+        self._multidiffusion = None
+
+    def _view_geometry(self, h8: int, w8: int) -> Optional[ViewGeometry]:
+        """The views of an ``h8 x w8`` latent, or None when the call is not a MultiDiffusion call (switch off, or the latent
+        not larger than the window)."""
+        md = self._multidiffusion
+        if md is None or (h8 <= md["window_size"] and w8 <= md["window_size"]):
+            return None
+        return view_geometry(h8, w8, md["window_size"], md["stride"])
+
+    def _view_chunks(self, nv: int, cfg: bool, device):
+        """Batch-row index tensors of the step-by-step loop's network calls under ``view_batch_size`` (both halves of a
+        guided batch together), or None for one call over all views."""
+        vb = self._multidiffusion["view_batch_size"]
+        if vb is None or vb >= nv:
+            return None
+        chunks = [torch.arange(s, min(s + vb, nv), device=device) for s in range(0, nv, vb)]
+        return [torch.cat([i, i + nv]) for i in chunks] if cfg else chunks
+
+    @staticmethod
+    def _blend_views(parts, geo: ViewGeometry):
+        """The per-step blend of the step-by-step loops: the latent groups ``parts`` ([N * V, c, wh, ww] each, one dtype) as ONE
+        latent through ``ops.view_blend`` -- what the on-device loop does to its master copy.  Returns (the blended
+        groups, the global fp32 [N, C, H, W])."""
+        cat = torch.cat(parts, dim=1) if len(parts) > 1 else parts[0]
+        master = cat.float().contiguous()
+        if master is cat or master.data_ptr() == cat.data_ptr():
+            master = cat.clone()
+        out = torch.empty(cat.shape, dtype=cat.dtype, device=cat.device)
+        glob = torch.empty(cat.shape[0] // geo.num_views, cat.shape[1], geo.height, geo.width, dtype=torch.float32, device=cat.device)
+        ops.view_blend(master, out, glob, geo, halves=1, round_master=cat.dtype != torch.float32)
+        return list(out.split([p_.shape[1] for p_ in parts], dim=1)), glob
+
     # ---- IP-Adapter image prompts (the reference's IPAdapterMixin, ref 11,125) ------------------------------
     def load_ip_adapter(self, pretrained_model_name_or_path_or_dict, subfolder: Optional[str] = None,
                         weight_name: Optional[str] = None, **kwargs):
@@ -136,9 +203,10 @@ class UniRendererPipeline:
         image_embeds = image_embeds.repeat_interleave(num_images_per_prompt, dim=0)
         return image_embeds, torch.zeros_like(image_embeds)
 
-    def _prepare_ip_adapter(self, ip_adapter_image, device, total: int, num_images_per_prompt: int):
+    def _prepare_ip_adapter(self, ip_adapter_image, device, total: int, num_images_per_prompt: int, views: int = 1):
         """Puts the image prompt of a sampling call into the UNet's static embedding buffer: ``total`` rows, under
-        classifier-free guidance ``[zeros ; embeds]`` in the order of ``_batch_prompt``."""
+        classifier-free guidance ``[zeros ; embeds]`` in the order of ``_batch_prompt``.  ``views`` > 1 (MultiDiffusion): every
+        row repeated for its sample's views."""
         loaded = self.unet.ip_adapter_state() is not None
         if ip_adapter_image is None:
             if loaded:
@@ -156,6 +224,9 @@ class UniRendererPipeline:
             if total % embeds.shape[0]:
                 raise ValueError(f"{embeds.shape[0]} image embeddings for a batch of {total}")
             embeds = embeds.repeat(total // embeds.shape[0], 1)
+            uncond = torch.zeros_like(embeds)
+        if views > 1:
+            embeds = embeds.repeat_interleave(views, dim=0)
             uncond = torch.zeros_like(embeds)
         if self.do_classifier_free_guidance:
             embeds = torch.cat([uncond, embeds])
@@ -454,7 +525,8 @@ class UniRendererPipeline:
         return key, g
 
     def _fused_loop(self, x_img, cond28, ehs, timesteps, sched, run_decoder: bool, lat_dtype=torch.float32,
-                    guidance: Optional[float] = None, cond_scale: float = 1.0, eta: float = 0.0, seed: Optional[int] = None):
+                    guidance: Optional[float] = None, cond_scale: float = 1.0, eta: float = 0.0, seed: Optional[int] = None,
+                    views: Optional[ViewGeometry] = None):
         """All denoise steps as replays of ONE graph = step + ur_ddim_update (prediction -> next input, in the
         graph's static input buffer) + ur_sampler_advance (step counter, next timestep).  UniPC: ur_unipc_update.  DDIM
         with eta != 0, DDPM, (SDE-)DPM-Solver++: ur_sde_update, whose noise is keyed by ``seed``, written into a device
@@ -462,7 +534,9 @@ class UniRendererPipeline:
         attribute channels of ``cond`` evolve at t_attr, the image latent is clean (t_img = 0); rendering direction:
         the 4 image channels of ``x_t`` evolve at t_img, the attributes are clean.  ``guidance``: classifier-free
         guidance -- the inputs hold cond + uncond halves (2B samples); the inverse direction guides the material group
-        only (pipeline.py:2695-2721), the rendering direction the whole image prediction (1642-1644)."""
+        only (pipeline.py:2695-2721), the rendering direction the whole image prediction (1642-1644).
+        ``views`` (MultiDiffusion): the batch is N * V views; ``ops.view_blend`` follows the update inside the graph, whose key
+        then holds the geometry (the launch bakes it in), and the result is the GLOBAL latent [N, C, H, W]."""
         n = len(timesteps)
         cfg = guidance is not None
         nb = x_img.shape[0] // 2 if cfg else x_img.shape[0]  # distinct latents
@@ -481,7 +555,7 @@ class UniRendererPipeline:
         else:
             coef, tvals = self._ddim_tables(sched, timesteps)
         kind = "unipc" if unipc else ("sde-" + type(sched).__name__ if sde else "ddim")
-        skey = key + (n, lat_dtype, guidance, self.precompute_time_tables, kind)
+        skey = key + (() if views is None else (("views",) + tuple(views),)) + (n, lat_dtype, guidance, self.precompute_time_tables, kind)
         st = self._sample_graphs.get(skey)
         if st is None:
             dev = x_img.device
@@ -497,6 +571,8 @@ class UniRendererPipeline:
             if sde:  # the previous prediction and the noise key (ur_sde_update)
                 st["hist"] = torch.zeros(mshape, dtype=torch.float32, device=dev)
                 st["seed"] = torch.zeros(1, dtype=torch.int64, device=dev)
+            if views is not None:  # the blended global latent (ur_view_blend writes it on every step)
+                st["global"] = torch.zeros((nb // views.num_views, mshape[1], views.height, views.width), dtype=torch.float32, device=dev)
 
             def update(pred_nhwc, c0, lat, cfg_channels):
                 if sde:
@@ -508,6 +584,8 @@ class UniRendererPipeline:
                 else:
                     ops.ddim_update(pred_nhwc, c0, lat, st["coef"], st["step"], n, master=st["master"],
                                     round_master=st["round_master"], guidance=guidance, cfg_channels=cfg_channels)
+                if views is not None:  # every view <- the mean of the views that cover each of its pixels
+                    ops.view_blend(st["master"], lat, st["global"], views, halves=2 if cfg else 1, round_master=st["round_master"])
 
             def post(out):
                 if run_decoder:  # the material group is channels 4..7 of the 28
@@ -546,7 +624,7 @@ class UniRendererPipeline:
                 g.pro.replay()
             st["graph"].replay()
         # a COPY: ``master`` is this sampling graph's static buffer and the next call with the same shapes overwrites it
-        return st["master"].to(lat_dtype, copy=True)
+        return st["master" if views is None else "global"].to(lat_dtype, copy=True)
 
     def _step(self, x_img, cond28, ehs, t_img, t_attr, run_decoder: bool, cond_scale: float = 1.0, sig=None, first: bool = True):
         """One step of a sampling loop.  ``first``: the first step of a loop (the hoisted executor runs its prologue on the
@@ -561,6 +639,25 @@ class UniRendererPipeline:
         tb = lambda t: torch.as_tensor(t, device=x_img.device).float().reshape(-1)
         return dual_stream_step(self.unet, self.controlnet, self.controldec, x_img.to(dt), cond28.to(dt), ehs.to(dt),
                                 tb(t_img), tb(t_attr), run_decoder, conditioning_scale=cond_scale)
+
+    def _step_chunked(self, chunks, fixed, x_img, cond28, ehs, t_img, t_attr, run_decoder: bool, **kw):
+        """``_step`` over the batch rows ``chunks[k]`` in turn (``view_batch_size``); the prediction the loop reads, assembled
+        for the whole batch.  ``fixed``: a dict the loop keeps for its call -- every chunk's fixed inputs are cut ONCE, so that the
+        hoisted executor sees one object per chunk (a chunk's prologue still re-runs when the previous call was another chunk's)."""
+        name = "attr_pred" if run_decoder else "img_pred"
+        full = None
+        for k, idx in enumerate(chunks):
+            if k not in fixed:
+                fixed[k] = ((x_img if run_decoder else cond28)[idx], ehs[idx])
+            if run_decoder:
+                (xi, e), ci = fixed[k], cond28[idx]
+            else:
+                (ci, e), xi = fixed[k], x_img[idx]
+            o = self._step(xi, ci, e, t_img, t_attr, run_decoder, **kw)[name]
+            if full is None:
+                full = torch.empty((x_img.shape[0],) + tuple(o.shape[1:]), dtype=o.dtype, device=o.device)
+            full[idx] = o  # the executor's output buffer is static: copy before the next chunk runs
+        return {name: full}
 
     # =====================================================================================================
     @torch.no_grad()
@@ -619,13 +716,20 @@ class UniRendererPipeline:
             image_latents = image_latents.repeat_interleave(num_images_per_prompt, dim=0)
             mask_latents = mask_latents.repeat_interleave(num_images_per_prompt, dim=0)
         prompt_embeds = self._batch_prompt(prompt_embeds, negative_prompt_embeds, total)
-        self._prepare_ip_adapter(ip_adapter_image, device, total, num_images_per_prompt)
         h8, w8 = image_latents.shape[-2:]
+        geo = self._view_geometry(h8, w8)  # MultiDiffusion: None unless enabled and the latent is larger than the window
+        self._prepare_ip_adapter(ip_adapter_image, device, total, num_images_per_prompt, views=geo.num_views if geo else 1)
         height, width = height or h8 * self.vae_scale_factor, width or w8 * self.vae_scale_factor
         nlat = self.unet.config.in_channels
         lat = {n: self.prepare_latents(total, nlat, height, width, prompt_embeds.dtype,
                                        device, generator, latents) for n in ATTR_GROUPS}
         cfg = self.do_classifier_free_guidance
+        glob = None
+        if geo is not None:  # the global tensors are cut into views ONCE per call; view v of sample n is batch row n * V + v
+            glob = torch.cat([lat[n] for n in ATTR_GROUPS], dim=1).float()
+            image_latents, mask_latents = gather_views(image_latents, geo), gather_views(mask_latents, geo)
+            lat = {n: gather_views(lat[n], geo) for n in ATTR_GROUPS}
+            prompt_embeds = prompt_embeds.repeat_interleave(geo.num_views, dim=0)
         dup = (lambda t: torch.cat([t, t])) if cfg else (lambda t: t)
         x_img = self.scheduler_img.scale_model_input(dup(image_latents), 0)
         x_mask = self.scheduler_img.scale_model_input(dup(mask_latents), 0)
@@ -639,11 +743,13 @@ class UniRendererPipeline:
             cond28 = torch.cat((x_mask.to(cat.dtype), cat), dim=1)
             fin = self._fused_loop(x_img, cond28, prompt_embeds, timesteps_attr, group_scheds[0], run_decoder=True,
                                    lat_dtype=cat.dtype, guidance=(float(self.guidance_scale) if cfg else None),
-                                   cond_scale=cond_scale, eta=eta, seed=seed)
+                                   cond_scale=cond_scale, eta=eta, seed=seed, views=geo)
             lat = {n: fin[:, 4 * k:4 * k + 4].to(lat[n].dtype) for k, n in enumerate(ATTR_GROUPS)}
+            glob = None  # ``fin`` is the global latent already
             timesteps_img = timesteps_attr = []  # loop below is skipped
         sig = self._weights_signature() if len(timesteps_attr) else None  # once per call, not per step
         seed_dev = torch.tensor([seed], dtype=torch.int64, device=device) if seed is not None and len(timesteps_attr) else None
+        chunks, chunk_fixed = (self._view_chunks(lat["material"].shape[0], cfg, device) if geo is not None and len(timesteps_attr) else None), {}
         with self.progress_bar(total=num_inference_steps) as bar:
             # the clean image latent's timestep is the constant 0 (ref 2476): hand the hoisted executor the SAME tensor object on every
             # step -- it re-runs its prologue when a fixed input changes identity (graph.GraphedHoistedStep.step), and the per-step
@@ -654,11 +760,17 @@ class UniRendererPipeline:
                 cat = torch.cat([dup(lat[n]) for n in ATTR_GROUPS], dim=1)
                 cat = self.scheduler_attr.scale_model_input(cat, t_attr)
                 cond28 = torch.cat((x_mask.to(cat.dtype), cat), dim=1)  # mask latent first: 4 + 6*4 = 28 channels
-                out = self._step(x_img, cond28, prompt_embeds, t_img, t_attr, run_decoder=True, cond_scale=cond_scale, sig=sig,
-                                 first=(i == 0))
+                if chunks is None:
+                    out = self._step(x_img, cond28, prompt_embeds, t_img, t_attr, run_decoder=True, cond_scale=cond_scale, sig=sig,
+                                     first=(i == 0))
+                else:
+                    out = self._step_chunked(chunks, chunk_fixed, x_img, cond28, prompt_embeds, t_img, t_attr, run_decoder=True,
+                                             cond_scale=cond_scale, sig=sig, first=(i == 0))
                 label_pred = out["attr_pred"][:, 4:]  # drop the mask group (ref 2691)
-                # the six groups are ONE 24-channel latent to the noise stream, as in the fused loop
-                noise = self._step_noise(seed, seed_dev, i, (total, 4 * len(ATTR_GROUPS), h8, w8), device)
+                # the six groups are ONE 24-channel latent to the noise stream, as in the fused loop (MultiDiffusion: over the
+                # [N * V, ...] view batch, so overlapping views draw independent noise)
+                nshape = (total, 4 * len(ATTR_GROUPS), h8, w8) if geo is None else (total * geo.num_views, 4 * len(ATTR_GROUPS), geo.wh, geo.ww)
+                noise = self._step_noise(seed, seed_dev, i, nshape, device)
                 for k, n in enumerate(ATTR_GROUPS):
                     pred = label_pred[:, 4 * k:4 * k + 4]
                     if cfg:
@@ -668,9 +780,14 @@ class UniRendererPipeline:
                     sch = getattr(self, f"scheduler_{n}")
                     kw_step = self._step_kwargs(sch, eta, None if noise is None else noise[:, 4 * k:4 * k + 4])
                     lat[n] = sch.step(pred, t_attr, lat[n], return_dict=False, **kw_step)[0]
+                if geo is not None:  # where the fused loop's graph has ur_view_blend
+                    parts, glob = self._blend_views([lat[n] for n in ATTR_GROUPS], geo)
+                    lat = dict(zip(ATTR_GROUPS, parts))
                 if callback_on_step_end is not None:
                     callback_on_step_end(self, i, t_attr, {"latents": lat["material"]})
                 bar.update()
+        if glob is not None:  # the step-by-step MultiDiffusion loop: the results are the global latents
+            lat = {n: glob[:, 4 * k:4 * k + 4].to(lat[n].dtype) for k, n in enumerate(ATTR_GROUPS)}
         if output_type == "latent":
             return tuple(lat[n] for n in ATTR_GROUPS)
         # the five image groups (ref 2755-2769: five vae.decode calls) decoded as ONE batch
@@ -724,11 +841,17 @@ class UniRendererPipeline:
             attr_latents = torch.cat(parts, dim=1)
         batch_size = attr_latents.shape[0]
         prompt_embeds = self._batch_prompt(prompt_embeds, negative_prompt_embeds, batch_size)
-        self._prepare_ip_adapter(ip_adapter_image, device, batch_size, num_images_per_prompt)
         h8, w8 = attr_latents.shape[-2:]
+        geo = self._view_geometry(h8, w8)  # MultiDiffusion (see real_image2mask_3mod_albedo)
+        self._prepare_ip_adapter(ip_adapter_image, device, batch_size, num_images_per_prompt, views=geo.num_views if geo else 1)
         height, width = height or h8 * self.vae_scale_factor, width or w8 * self.vae_scale_factor
         latents_img = self.prepare_latents(batch_size, 4, height, width, prompt_embeds.dtype, device, generator, latents)
         cfg = self.do_classifier_free_guidance
+        glob = None
+        if geo is not None:
+            glob = latents_img.float()
+            attr_latents, latents_img = gather_views(attr_latents, geo), gather_views(latents_img, geo)
+            prompt_embeds = prompt_embeds.repeat_interleave(geo.num_views, dim=0)
         dup = (lambda t: torch.cat([t, t])) if cfg else (lambda t: t)
         cond28 = dup(self.scheduler_img.scale_model_input(attr_latents, 0))
         eta = float(eta)
@@ -737,17 +860,23 @@ class UniRendererPipeline:
             latents_img = self._fused_loop(dup(latents_img), cond28, prompt_embeds, timesteps, self.scheduler_img,
                                            run_decoder=False, lat_dtype=latents_img.dtype,
                                            guidance=(float(self.guidance_scale) if cfg else None),
-                                           cond_scale=float(controlnet_conditioning_scale), eta=eta, seed=seed)
+                                           cond_scale=float(controlnet_conditioning_scale), eta=eta, seed=seed, views=geo)
+            glob = None  # the fused loop returned the global latent
             timesteps = timesteps[:0]  # loop below is skipped
         sig = self._weights_signature() if len(timesteps) else None
         seed_dev = torch.tensor([seed], dtype=torch.int64, device=device) if seed is not None and len(timesteps) else None
+        chunks, chunk_fixed = (self._view_chunks(latents_img.shape[0], cfg, device) if geo is not None and len(timesteps) else None), {}
         with self.progress_bar(total=num_inference_steps) as bar:
             t_attr_fixed = timesteps_attr[0] if len(timesteps) else None  # clean attributes: the constant 0, one object (see above)
             for i in range(len(timesteps)):
                 t_img, t_attr = timesteps[i], t_attr_fixed
                 x = self.scheduler_img.scale_model_input(dup(latents_img), t_img)
-                out = self._step(x, cond28, prompt_embeds, t_img, t_attr, run_decoder=False,
-                                 cond_scale=float(controlnet_conditioning_scale), sig=sig, first=(i == 0))
+                if chunks is None:
+                    out = self._step(x, cond28, prompt_embeds, t_img, t_attr, run_decoder=False,
+                                     cond_scale=float(controlnet_conditioning_scale), sig=sig, first=(i == 0))
+                else:
+                    out = self._step_chunked(chunks, chunk_fixed, x, cond28, prompt_embeds, t_img, t_attr, run_decoder=False,
+                                             cond_scale=float(controlnet_conditioning_scale), sig=sig, first=(i == 0))
                 img_pred = out["img_pred"]
                 if cfg:
                     p_cond, p_uncond = img_pred.chunk(2)  # ref 1642-1644
@@ -755,7 +884,11 @@ class UniRendererPipeline:
                 noise = self._step_noise(seed, seed_dev, i, tuple(latents_img.shape), device)
                 latents_img = self.scheduler_img.step(img_pred, t_img, latents_img, return_dict=False,
                                                       **self._step_kwargs(self.scheduler_img, eta, noise))[0]
+                if geo is not None:
+                    (latents_img,), glob = self._blend_views([latents_img], geo)
                 bar.update()
+        if glob is not None:
+            latents_img = glob.to(latents_img.dtype)
         if output_type == "latent":
             return latents_img
         return self._postprocess(self._vae_decode(latents_img, generator), output_type)
