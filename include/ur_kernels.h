@@ -643,7 +643,7 @@ int ur_unipc_update(const void* pred, int pred_ld, int pred_c0, void* lat, int64
                     int round_master, int cfg, float guidance, int cfg_channels, int dtype, void* stream);
 
 /*
- * ur_sde_update (csrc/sampler_sde.hip; an ADDITION to ABI 17, nothing existing changes): the update of the samplers that are a
+ * ur_sde_update (csrc/sampler.hip; an ADDITION to ABI 17, nothing existing changes): the update of the samplers that are a
  * linear multistep recurrence with a noise term for an x0-predicting model -- DDIM with eta, DDPM (fixed_small / fixed_large),
  * DPM-Solver++ 1 / 2M and SDE-DPM-Solver++ 1 / 2M (host: the coefficient_table() of schedulers.DDIMScheduler, DDPMScheduler,
  * DPMSolverMultistepScheduler, row i = p0 p1 p2 pn, fp32 [nsteps][4]):

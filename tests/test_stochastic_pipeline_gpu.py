@@ -106,7 +106,7 @@ def test_ddim_eta_zero_keeps_the_existing_kernel_and_draws_no_seed(dev, rig, mon
     """eta = 0 (the default and explicitly) must stay on ur_ddim_update: same sampling graph kind, ur_sde_update never
     launched, nothing drawn from the generator beyond what the call drew before -- so the bits are today's."""
     from uni_renderer_amd import ops
-    from uni_renderer_amd.pipeline import UniRendererPipeline
+    from uni_renderer_amd.schedulers import device_plan
 
     pipe, _, t = rig
     _attach(pipe, "ddim-eta1")  # plain DDIMScheduler objects
@@ -127,7 +127,8 @@ def test_ddim_eta_zero_keeps_the_existing_kernel_and_draws_no_seed(dev, rig, mon
         assert torch.equal(g1.get_state(), torch.Generator().manual_seed(8).get_state())  # latents were given: nothing drawn
     pipe.use_fused_sampler = True
     assert [k[-1] for k in pipe._sample_graphs] == ["ddim"]
-    assert UniRendererPipeline._sde_table(pipe.scheduler_img, 0.0) is None
+    plan = device_plan(pipe.scheduler_img, 0.0)
+    assert plan.kind == "ddim" and not plan.noisy  # eta = 0 keeps the existing update: no ur_sde_update table
 
 
 @pytest.mark.parametrize("name", ["ddim-eta1", "sde-dpm++2m"])

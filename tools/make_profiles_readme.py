@@ -155,6 +155,46 @@ incl. the inverse branch at SD size, the VAE, the RCCL world-size-1 collectives)
 `{tag}_loop_bench.json` (50-step DDIM loops; 20-step UniPC x 5 repeats as five calls vs one folded batch),
 `{tag}_train_graph/eager.json` (`tools/train_bench.py`; `{tag}_train_graph_torch_adamw.json`: the same with torch's fused AdamW instead
 of `optim.FusedAdamW`), `{tag}_vae_bench.json` (`tools/vae_bench.py`); round 2's A/B logs stay as `r02_*`.
+`tile_table_ab.txt` (the igemm tile builds moved into one generated table, `csrc/igemm_tiles.h`, and one split-K second-pass
+launcher: the tree before against the tree after, `bench.py --steps 100 --warmup 10` alternating on one box, with the comparison of
+the `--dump-outputs` arrays; device code identical, so this only shows the host side costs nothing).
+`launch_layer_ab.txt` (the host launch layer `csrc/ur_launch.h` and the one segment table of the five multi-tensor kernels: device
+assembly function by function, argument-struct sizes, line counts, output / training identity and the alternating speed lines).
+`adamw8bit_ab.txt` (`optim.AdamW8bit` against `optim.FusedAdamW` in the graphed training step: `tools/train_bench.py --graph` and
+`--graph --adamw8bit` alternating three times each on one box, `peak_mem_gb` of both arms, and the optimizer kernels' rows of two
+separate `rocprofv3 --kernel-trace --stats` runs, with the kernel's resource usage and instruction counts).
+`ema_ab.txt` (`tools/ema_ab.py`: the EMA update of the SD-1.x sized networks' fp32 masters -- `EMAModel.step` launched from Python and as
+a graph replay, with plain and with non-temporal shadow accesses (the plain variant was removed after this run), against the per-parameter torch loop of diffusers 0.24 and its `torch._foreach`
+form, with the achieved TB/s against 12 B per parameter and the kernels' rows of a separate `rocprofv3 --kernel-trace --stats` run;
+`tools/train_bench.py --graph` on the parent twice, on this tree and with `--ema`, alternating processes, three rounds).
+`ip_adapter_ab.txt` (`tools/ip_adapter_ab.py --parent <built checkout of the parent commit>`: `ur_ip_attention_add` at the four levels of
+the SD-1.x UNet, both thread mappings and a sweep of the groups walked per workgroup, against torch's SDPA + scale + add on the same tensors
+and against a device copy of the same bytes; the captured step and the 50-step rendering loop with the adapter off / on and off on the
+parent commit, alternating processes, with launch counts and output checksums; section 3, by hand: the earlier variants of the kernel).
+`lora_ab.txt` (`tools/lora_ab.py`: the grouped LoRA merge `ur_lora_merge_multi` at SD-1.x UNet size, rank 4 / 16 / 64 / 128, against the
+same merge written per layer in torch; a whole scale switch through the pipeline; `bench.py` on the parent and on this tree).
+`lora_train_ab.txt` (training a UNet LoRA adapter: the two kernels `ur_lora_merge_cast_multi` / `ur_lora_grad_multi` at SD-1.x UNet size
+(`tools/lora_train_ab.py`), the captured training step of `tools/train_bench.py --graph` as a full fine-tune on the parent and on this
+tree and with `--lora-rank 4 / 16 / 64`, with and without `--freeze-exchange-nets`, step time and peak memory; the measured
+gradient errors behind the bounds of `tests/test_lora_train_gpu.py`; `bench.py` on the parent and on this tree).
+`pack_recipes_ab.txt` (the packed operands moved behind the recipes of `uni_renderer_amd/packs.py`: output and launch-record identity
+of every executor against the tree before, and the host-side timings -- headline step, first call, LoRA scale switch, eager
+module-path step -- of both trees alternating on one box).
+`stochastic_samplers_ab.txt` (`tools/stochastic_ab.py`: the 50-step inverse / rendering loops under DDIM eta 0 on the parent and on
+this tree in alternating processes with the observed spread, the same loops under UniPC, DDIM eta 1, DDPM, DPM-Solver++ 2M and its
+SDE variant fused and step by step, and `ur_sde_update` with / without noise against `ur_unipc_update` at `[4, 24, 64, 64]` and
+`[4, 4, 64, 64]`).
+`multidiffusion_ab.txt` (`tools/multidiffusion_ab.py`: `ur_view_blend` alone at `[9, 24, 64, 64]` and `[81, 24, 64, 64]` against the torch
+composition of the same arithmetic and against copies of its bytes; the 50-step loops on one 1024 x 1024 image natively, with nine
+views fused and step by step and with 81 views, time and peak memory; the 512 x 512 loops with the switch off on this tree and on the
+parent in alternating processes with the observed spread).
+`vae_tiling_ab.txt` (`tools/vae_tiling_bench.py`: a tiled decode of a 1024 x 1024 image through the SD-size VAE -- the fused stitch
+`ur_blend_tiles` against diffusers' torch loops over the same nine tiles, whole `tiled_decode` calls with either, with one tile per
+network call, the plain decode, and peak allocated memory of each).
+`sampler_plan_ab.txt` (one `schedulers.device_plan` per scheduler, one loop body for both directions, the three update kernels in
+`csrc/sampler.hip`: device assembly function by function, the latents of every sampler / guidance / latent dtype / MultiDiffusion
+call of the tree before against the tree after, fused and step by step, `bench.py`'s `loop_parity` numbers, the alternating speed
+lines of the 50-step loops and the folded UniPC call, line counts).
 
 | file | what |
 |---|---|

@@ -255,151 +255,6 @@ extern "C" int ur_nhwc_to_nchw(const void* src, int dtype, int B, int C, int H, 
     UR_DISPATCH(dtype, return to_nchw_dst<T>(src, B, C, H, W, dst, dst_dtype, s));
 }
 
-// ------------------------------------------------------------------------------------------
-// On-device sampler update: the DDIM (eta = 0) step of models/pipeline.py:2691-2730 /
-// 1645-1649 for a model that predicts x0 ("sample"), applied to C latent channels at once, with the per-step
-// scalars read from a device table indexed by a device-side step counter -- so a whole sampling loop is graph
-// replays with no host round trip.  Same operation order as the scheduler's fp32 torch expression (no FMA
-// contraction), so the fused loop reproduces the unfused one bit for bit:
-//     eps  = (x - sqrt(a_t) * x0) / sqrt(1 - a_t);   x' = sqrt(a_prev) * x0 + sqrt(1 - a_prev) * eps
-// pred: NHWC [B][HW][pred_ld], channels pred_c0 .. pred_c0 + C.   lat: NCHW [B][C][HW] with batch stride lat_bs.
-// master (optional, contiguous fp32 [B][C][HW]): the sampler's own copy of the latents -- the reference keeps them
-// in the caller's dtype (fp32 in eval) between steps and only the network input is rounded to fp16/bf16.
-// ------------------------------------------------------------------------------------------
-template <typename T>
-__global__ void __launch_bounds__(256) ddim_update_kernel(const T* __restrict__ pred, int pred_ld, int pred_c0,
-                                                          T* __restrict__ lat, int64_t lat_bs, int C, int B, int HW,
-                                                          const float* __restrict__ coef, const int* __restrict__ step,
-                                                          int nsteps, float* __restrict__ master, int round_master,
-                                                          int cfg, float guidance, int cfg_channels) {
-#pragma clang fp contract(off)
-    const int st = min(*step, nsteps - 1);
-    const float s_at = coef[4 * st + 0], s_1mat = coef[4 * st + 1], s_ap = coef[4 * st + 2], s_1map = coef[4 * st + 3];
-    const int64_t total = (int64_t)B * C * HW;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-        const int p = (int)(i % HW);
-        const int64_t bc = i / HW;
-        const int c = (int)(bc % C), b = (int)(bc / C);
-        T* xp = lat + (int64_t)b * lat_bs + (int64_t)c * HW + p;
-        const float x = master ? master[i] : (float)*xp;
-        T x0t = pred[((int64_t)b * HW + p) * pred_ld + pred_c0 + c];
-        if (cfg && c < cfg_channels) {
-            // classifier-free guidance as the reference's loop evaluates it in the prediction's dtype (every
-            // operation rounded): pred = p_uncond + g * (p_cond - p_uncond), cond = samples [0, B), uncond = [B, 2B)
-            const T pu = pred[((int64_t)(b + B) * HW + p) * pred_ld + pred_c0 + c];
-            const T d = (T)((float)x0t - (float)pu);
-            const T m = (T)((float)d * guidance);
-            x0t = (T)((float)pu + (float)m);
-        }
-        const float x0 = (float)x0t;
-        const float eps = (x - s_at * x0) / s_1mat;
-        const float a = s_ap * x0;
-        const float e = s_1map * eps;
-        const float v = a + e;
-        *xp = (T)v;
-        if (cfg) xp[(int64_t)B * lat_bs] = (T)v;  // the uncond half of the next input is the same latent
-        if (master) master[i] = round_master ? (float)(T)v : v;
-    }
-}
-
-// UniPC (order <= 2, x0 / data prediction, B(h) = bh2) predictor-corrector update as ONE pass (schedulers.py
-// UniPCMultistepScheduler.coefficient_table): with m_i the model's x0 prediction at step i,
-//     L_i     = c0 L_{i-1} + c1 m_{i-1} + c2 m_{i-2} + c3 m_i      corrected sample ("last_sample"; step 0: L_0 = x_0)
-//     x_{i+1} = p0 L_i     + p1 m_i     + p2 m_{i-1}               next model input
-// coef row i = (c0, c1, c2, c3, p0, p1, p2, -).  `last` holds L, `xmaster` the evolving x (what the loop returns), `hist`
-// the two previous predictions in a 2-slot ring indexed by the device step counter (m_{i-1} in slot (i+1)&1, m_{i-2}
-// in slot i&1, which m_i then overwrites).  All fp32; with round_master the samples are rounded through the latent dtype
-// where the reference's scheduler casts them (`x_t.to(x.dtype)`).
-template <typename T>
-__global__ void __launch_bounds__(256) unipc_update_kernel(const T* __restrict__ pred, int pred_ld, int pred_c0, T* __restrict__ lat,
-                                                           int64_t lat_bs, int C, int B, int HW, const float* __restrict__ coef,
-                                                           const int* __restrict__ step, int nsteps, float* __restrict__ last,
-                                                           float* __restrict__ xmaster, float* __restrict__ hist, int round_master,
-                                                           int cfg, float guidance, int cfg_channels) {
-    const int st = min(*step, nsteps - 1);
-    const float* cr = coef + (int64_t)st * 8;
-    const float c0 = cr[0], c1 = cr[1], c2 = cr[2], c3 = cr[3], p0 = cr[4], p1 = cr[5], p2 = cr[6];
-    const int64_t total = (int64_t)B * C * HW;
-    float* h1 = hist + (int64_t)((st + 1) & 1) * total;  // m_{i-1}
-    float* h2 = hist + (int64_t)(st & 1) * total;        // m_{i-2}, then m_i
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-        const int p = (int)(i % HW);
-        const int64_t bc = i / HW;
-        const int c = (int)(bc % C), b = (int)(bc / C);
-        T mt = pred[((int64_t)b * HW + p) * pred_ld + pred_c0 + c];
-        if (cfg && c < cfg_channels) {  // as in ddim_update_kernel: the reference's guidance arithmetic in the prediction's dtype
-            const T pu = pred[((int64_t)(b + B) * HW + p) * pred_ld + pred_c0 + c];
-            const T d = (T)((float)mt - (float)pu);
-            const T m = (T)((float)d * guidance);
-            mt = (T)((float)pu + (float)m);
-        }
-        const float m = (float)mt, m1 = h1[i], m2 = h2[i];
-        float L = c0 * last[i] + c1 * m1 + c2 * m2 + c3 * m;
-        if (round_master) L = (float)(T)L;
-        float x = p0 * L + p1 * m + p2 * m1;
-        const T xt = (T)x;
-        if (round_master) x = (float)xt;
-        last[i] = L;
-        xmaster[i] = x;
-        h2[i] = m;
-        T* xp = lat + (int64_t)b * lat_bs + (int64_t)c * HW + p;
-        *xp = xt;
-        if (cfg) xp[(int64_t)B * lat_bs] = xt;
-    }
-}
-
-// step += 1; t_out[0..B) = tsteps[step] (the timestep the NEXT replay denoises at)
-__global__ void sampler_advance_kernel(int* step, const float* __restrict__ tsteps, int nsteps, float* t_out, int B) {
-    // ONE thread reads the counter and shares it through LDS: with every thread reading *step, waves 1-3 could see
-    // the value thread 0 had already incremented and write tsteps[st + 1] for the samples beyond the first 64
-    __shared__ int st_sh;
-    if (threadIdx.x == 0) {
-        st_sh = *step + 1;
-        *step = st_sh;
-    }
-    __syncthreads();
-    const int st = st_sh;
-    if (t_out && (int)threadIdx.x < B) t_out[threadIdx.x] = tsteps[min(st, nsteps - 1)];
-}
-
-extern "C" int ur_ddim_update(const void* pred, int pred_ld, int pred_c0, void* lat, int64_t lat_bstride, int C, int B,
-                              int HW, const float* coef, const int* step, int nsteps, float* master, int round_master,
-                              int cfg, float guidance, int cfg_channels, int dtype, void* stream) {
-    if (!pred || !lat || !coef || !step || C <= 0 || B <= 0 || HW <= 0 || nsteps <= 0 || pred_c0 < 0 ||
-        pred_c0 + C > pred_ld)
-        return UR_E_BADARG;
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    const int64_t total = (int64_t)B * C * HW;
-    const int grid = (int)((total + 255) / 256 > 2048 ? 2048 : (total + 255) / 256);
-    UR_DISPATCH(dtype, hipLaunchKernelGGL((ddim_update_kernel<T>), dim3(grid), dim3(256), 0, s, (const T*)pred, pred_ld,
-                       pred_c0, (T*)lat, lat_bstride, C, B, HW, coef, step, nsteps, master, round_master, cfg, guidance,
-                       cfg_channels));
-    return last_error();
-}
-
-extern "C" int ur_unipc_update(const void* pred, int pred_ld, int pred_c0, void* lat, int64_t lat_bstride, int C, int B,
-                               int HW, const float* coef, const int* step, int nsteps, float* last, float* xmaster,
-                               float* hist, int round_master, int cfg, float guidance, int cfg_channels, int dtype,
-                               void* stream) {
-    if (!pred || !lat || !coef || !step || !last || !xmaster || !hist || C <= 0 || B <= 0 || HW <= 0 || nsteps <= 0 ||
-        pred_c0 < 0 || pred_c0 + C > pred_ld)
-        return UR_E_BADARG;
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    const int64_t total = (int64_t)B * C * HW;
-    const int grid = (int)((total + 255) / 256 > 2048 ? 2048 : (total + 255) / 256);
-    UR_DISPATCH(dtype, hipLaunchKernelGGL((unipc_update_kernel<T>), dim3(grid), dim3(256), 0, s, (const T*)pred, pred_ld,
-                       pred_c0, (T*)lat, lat_bstride, C, B, HW, coef, step, nsteps, last, xmaster, hist, round_master, cfg,
-                       guidance, cfg_channels));
-    return last_error();
-}
-
-extern "C" int ur_sampler_advance(int* step, const float* tsteps, int nsteps, float* t_out, int B, void* stream) {
-    if (!step || !tsteps || nsteps <= 0 || B < 0 || B > 256) return UR_E_BADARG;
-    hipLaunchKernelGGL(sampler_advance_kernel, dim3(1), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), step, tsteps,
-                       nsteps, t_out, B);
-    return last_error();
-}
-
 // dst[k][0..bytes_k) = src[k][*step][0..bytes_k) for up to 4 tables: the rows of the CURRENT step of per-step tables a sampling
 // loop's prologue computed for all its steps (the time projections of every resnet: a function of the timestep only).
 struct StepRows { const char* src[4]; char* dst[4]; int64_t bytes[4]; };

@@ -844,6 +844,43 @@ def attention(q, k, vt, *, B, H, Tq, Tk, d, ldq, ldk, q_off=0, k_off=0, scale=No
     return o
 
 
+def _sampler_update_args(name: str, pred_nhwc, c0: int, lat_nchw, coef, step, nsteps: int, guidance, cfg_channels: int,
+                         round_master: bool, width: Optional[int], states, strict: bool = False):
+    """The validation ``ddim_update`` / ``unipc_update`` / ``sde_update`` share, and their common arguments: returns (the C
+    entry point's leading arguments pred .. nsteps, its trailing arguments round_master .. stream).  ``width``: the table's
+    row length (None: unchecked); ``states``: (tensor, leading dimensions) of every fp32 state buffer [..., B, C, H, W] with B
+    the number of distinct latents.  ``strict`` (``sde_update``): fp32 latents allowed, and the table, ``pred`` and
+    ``cfg_channels`` are checked against the shapes as well."""
+    _require_gpu(pred_nhwc)
+    B, Cc, H, W = lat_nchw.shape
+    cfg = guidance is not None
+    if cfg:
+        if B % 2 or pred_nhwc.shape[0] != B:
+            raise RuntimeError(f"{name}: guidance needs cond + uncond halves")
+        B //= 2
+    if lat_nchw.stride(3) != 1 or lat_nchw.stride(2) != W or lat_nchw.stride(1) != H * W:
+        raise RuntimeError(f"{name}: latent slice must have contiguous channel planes")
+    codes = DT_ANY if strict else DT
+    ok = pred_nhwc.dtype == lat_nchw.dtype and coef.dtype == torch.float32 and step.dtype == torch.int32 \
+        and (width is None or coef.shape[-1] == width)
+    if strict:
+        ok = ok and lat_nchw.dtype in codes and coef.dim() == 2 and coef.shape[0] >= nsteps and coef.is_contiguous()
+    if not ok:
+        raise RuntimeError(f"{name}: dtype / table mismatch")
+    if strict:
+        if pred_nhwc.dim() != 4 or not pred_nhwc.is_contiguous() or tuple(pred_nhwc.shape[:3]) != (lat_nchw.shape[0], H, W):
+            raise RuntimeError(f"{name}: pred must be a contiguous NHWC [B, H, W, Cp] tensor over the same samples and pixels")
+        if not 0 <= cfg_channels <= Cc:
+            raise RuntimeError(f"{name}: cfg_channels outside [0, C]")
+    for t, lead in states:
+        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != tuple(lead) + (B, Cc, H, W)):
+            raise RuntimeError(f"{name}: state buffers must be contiguous fp32 {list(lead) + ['B', 'C', 'H', 'W']} tensors")
+    head = (pred_nhwc.data_ptr(), pred_nhwc.shape[-1], c0, lat_nchw.data_ptr(), lat_nchw.stride(0), Cc, B, H * W,
+            coef.data_ptr(), step.data_ptr(), nsteps)
+    tail = (int(round_master), int(cfg), float(guidance or 0.0), int(cfg_channels), codes[lat_nchw.dtype], _stream())
+    return head, tail
+
+
 def ddim_update(pred_nhwc, c0: int, lat_nchw, coef, step, nsteps: int, master=None, round_master: bool = False,
                 guidance: Optional[float] = None, cfg_channels: int = 0):
     """In-place DDIM (x0-prediction) update of the NCHW latent slice ``lat_nchw`` [B, C, H, W] (batch stride free,
@@ -852,25 +889,9 @@ def ddim_update(pred_nhwc, c0: int, lat_nchw, coef, step, nsteps: int, master=No
     ``master``: optional contiguous fp32 [B, C, H, W] copy that carries the latents between steps.
     ``guidance`` (classifier-free): pred / lat hold 2B samples (cond, uncond), ``master`` B; the first ``cfg_channels``
     channels are guided."""
-    _require_gpu(pred_nhwc)
-    lib = _lib.load()
-    B, Cc, H, W = lat_nchw.shape
-    cfg = guidance is not None
-    if cfg:
-        if B % 2 or pred_nhwc.shape[0] != B:
-            raise RuntimeError("ddim_update: guidance needs cond + uncond halves")
-        B //= 2
-    if lat_nchw.stride(3) != 1 or lat_nchw.stride(2) != W or lat_nchw.stride(1) != H * W:
-        raise RuntimeError("ddim_update: latent slice must have contiguous channel planes")
-    if pred_nhwc.dtype != lat_nchw.dtype or coef.dtype != torch.float32 or step.dtype != torch.int32:
-        raise RuntimeError("ddim_update: dtype mismatch")
-    if master is not None and (master.dtype != torch.float32 or not master.is_contiguous()
-                               or tuple(master.shape) != (B, Cc, H, W)):
-        raise RuntimeError("ddim_update: master must be a contiguous fp32 [B, C, H, W] tensor")
-    check(lib.ur_ddim_update(pred_nhwc.data_ptr(), pred_nhwc.shape[-1], c0, lat_nchw.data_ptr(), lat_nchw.stride(0), Cc,
-                             B, H * W, coef.data_ptr(), step.data_ptr(), nsteps, _ptr(master), int(round_master),
-                             int(cfg), float(guidance or 0.0), int(cfg_channels), DT[lat_nchw.dtype], _stream()),
-          "ur_ddim_update")
+    head, tail = _sampler_update_args("ddim_update", pred_nhwc, c0, lat_nchw, coef, step, nsteps, guidance, cfg_channels,
+                                      round_master, None, [(master, ())])
+    check(_lib.load().ur_ddim_update(*head, _ptr(master), *tail), "ur_ddim_update")
 
 
 def unipc_update(pred_nhwc, c0: int, lat_nchw, coef, step, nsteps: int, last, xmaster, hist, round_master: bool = False,
@@ -879,25 +900,9 @@ def unipc_update(pred_nhwc, c0: int, lat_nchw, coef, step, nsteps: int, last, xm
     from channels c0.. of the NHWC prediction (include/ur_kernels.h ``ur_unipc_update``); ``coef`` [nsteps, 8] from
     ``schedulers.UniPCMultistepScheduler.coefficient_table``; ``last`` / ``xmaster`` fp32 [B, C, H, W], ``hist`` fp32
     [2, B, C, H, W] (zero before step 0).  ``guidance``: as in ``ddim_update``."""
-    _require_gpu(pred_nhwc)
-    lib = _lib.load()
-    B, Cc, H, W = lat_nchw.shape
-    cfg = guidance is not None
-    if cfg:
-        if B % 2 or pred_nhwc.shape[0] != B:
-            raise RuntimeError("unipc_update: guidance needs cond + uncond halves")
-        B //= 2
-    if lat_nchw.stride(3) != 1 or lat_nchw.stride(2) != W or lat_nchw.stride(1) != H * W:
-        raise RuntimeError("unipc_update: latent slice must have contiguous channel planes")
-    if pred_nhwc.dtype != lat_nchw.dtype or coef.dtype != torch.float32 or step.dtype != torch.int32 or coef.shape[-1] != 8:
-        raise RuntimeError("unipc_update: dtype / table mismatch")
-    for t, shp in ((last, (B, Cc, H, W)), (xmaster, (B, Cc, H, W)), (hist, (2, B, Cc, H, W))):
-        if t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != shp:
-            raise RuntimeError("unipc_update: state buffers must be contiguous fp32 [B, C, H, W] / [2, B, C, H, W]")
-    check(lib.ur_unipc_update(pred_nhwc.data_ptr(), pred_nhwc.shape[-1], c0, lat_nchw.data_ptr(), lat_nchw.stride(0), Cc,
-                              B, H * W, coef.data_ptr(), step.data_ptr(), nsteps, last.data_ptr(), xmaster.data_ptr(),
-                              hist.data_ptr(), int(round_master), int(cfg), float(guidance or 0.0), int(cfg_channels),
-                              DT[lat_nchw.dtype], _stream()), "ur_unipc_update")
+    head, tail = _sampler_update_args("unipc_update", pred_nhwc, c0, lat_nchw, coef, step, nsteps, guidance, cfg_channels,
+                                      round_master, 8, [(last, ()), (xmaster, ()), (hist, (2,))])
+    check(_lib.load().ur_unipc_update(*head, last.data_ptr(), xmaster.data_ptr(), hist.data_ptr(), *tail), "ur_unipc_update")
 
 
 def _seed_ptr(seed, what: str):
@@ -915,31 +920,10 @@ def sde_update(pred_nhwc, c0: int, lat_nchw, coef, step, nsteps: int, seed, mast
     from the scheduler's ``coefficient_table``; ``master`` / ``hist`` fp32 [B, C, H, W] (``hist`` zero before step 0);
     ``seed`` one device int64 that keys the noise ``xi`` the kernel draws itself (``sampler_noise`` is the same stream).
     fp16 / bf16 / fp32 latents.  ``guidance``: as in ``ddim_update``."""
-    _require_gpu(pred_nhwc)
-    lib = _lib.load()
-    B, Cc, H, W = lat_nchw.shape
-    cfg = guidance is not None
-    if cfg:
-        if B % 2 or pred_nhwc.shape[0] != B:
-            raise RuntimeError("sde_update: guidance needs cond + uncond halves")
-        B //= 2
-    if lat_nchw.stride(3) != 1 or lat_nchw.stride(2) != W or lat_nchw.stride(1) != H * W:
-        raise RuntimeError("sde_update: latent slice must have contiguous channel planes")
-    if (pred_nhwc.dtype != lat_nchw.dtype or lat_nchw.dtype not in DT_ANY or coef.dtype != torch.float32
-            or step.dtype != torch.int32 or coef.dim() != 2 or coef.shape[-1] != 4 or coef.shape[0] < nsteps
-            or not coef.is_contiguous()):
-        raise RuntimeError("sde_update: dtype / table mismatch")
-    if pred_nhwc.dim() != 4 or not pred_nhwc.is_contiguous() or tuple(pred_nhwc.shape[:3]) != (lat_nchw.shape[0], H, W):
-        raise RuntimeError("sde_update: pred must be a contiguous NHWC [B, H, W, Cp] tensor over the same samples and pixels")
-    if not 0 <= cfg_channels <= Cc:
-        raise RuntimeError("sde_update: cfg_channels outside [0, C]")
-    for t in (master, hist):
-        if t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != (B, Cc, H, W):
-            raise RuntimeError("sde_update: master / hist must be contiguous fp32 [B, C, H, W]")
-    check(lib.ur_sde_update(pred_nhwc.data_ptr(), pred_nhwc.shape[-1], c0, lat_nchw.data_ptr(), lat_nchw.stride(0), Cc, B,
-                            H * W, coef.data_ptr(), step.data_ptr(), nsteps, _seed_ptr(seed, "sde_update"), master.data_ptr(),
-                            hist.data_ptr(), int(round_master), int(cfg), float(guidance or 0.0), int(cfg_channels),
-                            DT_ANY[lat_nchw.dtype], _stream()), "ur_sde_update")
+    head, tail = _sampler_update_args("sde_update", pred_nhwc, c0, lat_nchw, coef, step, nsteps, guidance, cfg_channels,
+                                      round_master, 4, [(master, ()), (hist, ())], strict=True)
+    check(_lib.load().ur_sde_update(*head, _seed_ptr(seed, "sde_update"), master.data_ptr(), hist.data_ptr(), *tail),
+          "ur_sde_update")
 
 
 def sampler_noise(seed, step: int, shape, out=None):

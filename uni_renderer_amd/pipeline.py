@@ -29,11 +29,55 @@ from .ip_adapter import read_ip_adapter_file
 from .multidiffusion import ViewGeometry, gather_views, view_geometry
 from .lora import read_lora_file, scale_of
 from .graph import GraphedDualStreamStep, GraphedHoistedStep, dual_stream_step
-from .schedulers import DDIMScheduler, retrieve_timesteps
+from .schedulers import DDIMScheduler, device_plan, retrieve_timesteps
 from .unet_2d_blocks import freeu_state
 
 SCHEDULER_NAMES = ("img", "attr", "material", "albedo", "normal", "spec_light", "diff_light", "env")
 ATTR_GROUPS = ("material", "normal", "albedo", "spec_light", "diff_light", "env")  # after the mask group
+
+
+class _SamplerState:
+    """The device state one captured sampling loop carries between its replays, for a ``schedulers.DevicePlan`` kind: the step
+    counter, the plan's table and timesteps, the fp32 master copy of the evolving latent and what the kind's update kernel
+    keeps besides -- UniPC: the corrected sample L and the two previous predictions (``ur_unipc_update``); ``sde-*``: the
+    previous prediction and the noise key (``ur_sde_update``).  The graph knows the buffers, ``reset`` writes their values."""
+
+    def __init__(self, kind: str, nsteps: int, width: int):
+        self.kind, self.n, self.width = kind, nsteps, width
+
+    def allocate(self, mshape, dev, round_master: bool):
+        z = lambda *lead: torch.zeros(lead + tuple(mshape), dtype=torch.float32, device=dev)
+        self.round_master = round_master
+        self.step = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.coef, self.tvals, self.master = torch.zeros(self.n, self.width, device=dev), torch.zeros(self.n, device=dev), z()
+        if self.kind == "unipc":
+            self.last, self.hist = z(), z(2)
+        elif self.kind != "ddim":
+            self.hist, self.seed = z(), torch.zeros(1, dtype=torch.int64, device=dev)
+
+    def reset(self, x0, seed: Optional[int], plan):
+        """Step 0 of a call: ``plan``'s table (same kind and length; its values may differ from the last call's), the initial
+        sample ``x0``, the call's noise key."""
+        self.step.zero_()
+        self.coef.copy_(plan.coef)
+        self.tvals.copy_(plan.tvals)
+        self.master.copy_(x0)
+        if self.kind == "unipc":
+            self.last.copy_(self.master)  # L_0 = the initial sample
+            self.hist.zero_()
+        elif self.kind != "ddim":
+            self.hist.zero_()
+            self.seed.fill_(0 if seed is None else seed)
+
+    def update(self, pred_nhwc, c0: int, lat, guidance: Optional[float], cfg_channels: int):
+        """The kind's update kernel: prediction -> next input ``lat``, at the device-side step."""
+        kw = dict(round_master=self.round_master, guidance=guidance, cfg_channels=cfg_channels)
+        if self.kind == "ddim":
+            ops.ddim_update(pred_nhwc, c0, lat, self.coef, self.step, self.n, master=self.master, **kw)
+        elif self.kind == "unipc":
+            ops.unipc_update(pred_nhwc, c0, lat, self.coef, self.step, self.n, self.last, self.master, self.hist, **kw)
+        else:
+            ops.sde_update(pred_nhwc, c0, lat, self.coef, self.step, self.n, self.seed, self.master, self.hist, **kw)
 
 
 class UniRendererPipeline:
@@ -396,56 +440,41 @@ class UniRendererPipeline:
 
     # ---- one denoise step of the three networks ----------------------------------------------------------
     # ---- on-device sampling loop -------------------------------------------------------------
-    def _fusable(self, scheds, device, cond_scale, callback) -> bool:
-        """The fused loop covers what eval needs: this package's DDIM (x0 prediction, any eta), UniPC (order <= 2, x0
-        prediction, bh2 -- the scheduler eval/test_real.py:485-492 attaches), DDPM or DPM-Solver++ on every latent group with
-        one common schedule and configuration, with or without classifier-free guidance, no per-step callback, HIP graph on.  Anything else takes
-        the step-by-step loop below (identical results: tests/test_pipeline_gpu.py)."""
-        from .schedulers import DDIMScheduler, DDPMScheduler, DPMSolverMultistepScheduler, UniPCMultistepScheduler
-
+    def _fusable(self, scheds, device, cond_scale, callback, eta: float = 0.0) -> bool:
+        """The fused loop covers what eval needs: a scheduler with a device plan (``schedulers.device_plan``: this package's
+        DDIM with any eta, UniPC, DDPM, DPM-Solver++; x0 prediction) on every latent group with one common schedule and
+        configuration, with or without classifier-free guidance, no per-step callback, HIP graph on.  Anything else takes the
+        step-by-step loop (identical results: tests/test_pipeline_gpu.py)."""
         if not (self.use_fused_sampler and self.use_hip_graph and torch.device(device).type == "cuda"):
             return False
         if callback is not None:
             return False
-        s0 = scheds[0]
-        if type(s0) not in (DDIMScheduler, UniPCMultistepScheduler, DDPMScheduler, DPMSolverMultistepScheduler):
+        s0, p0 = scheds[0], device_plan(scheds[0], eta)
+        if p0 is None:
             return False
+        own_final = hasattr(s0, "final_alpha_cumprod")  # DDIM: the schedule is its tensors; the others': their configuration
         for s in scheds:
-            if type(s) is not type(s0) or s.prediction_type != "sample":
+            plan = device_plan(s, eta)
+            if plan is None or plan.kind != p0.kind or s.prediction_type != "sample":
                 return False
             if s.num_inference_steps != s0.num_inference_steps or not torch.equal(s.timesteps.cpu(), s0.timesteps.cpu()):
                 return False
             if not torch.equal(s.alphas_cumprod, s0.alphas_cumprod):
                 return False
-            if type(s0) is DDIMScheduler and float(s.final_alpha_cumprod) != float(s0.final_alpha_cumprod):
+            if own_final and float(s.final_alpha_cumprod) != float(s0.final_alpha_cumprod):
                 return False
-            if type(s0) is not DDIMScheduler and s.config != s0.config:
+            if not own_final and s.config != s0.config:
                 return False
         return True
 
-    # ---- stochastic samplers (DDIM with eta, DDPM, SDE-DPM-Solver++) and DPM-Solver++ ------------------------------
-    @staticmethod
-    def _sde_table(sched, eta: float):
-        """The [n, 4] table of ``ur_sde_update`` for ``sched``, or None where the loops keep their existing update (DDIM with
-        eta = 0, UniPC, a foreign scheduler object)."""
-        from .schedulers import DDIMScheduler, DDPMScheduler, DPMSolverMultistepScheduler
-
-        if type(sched) is DDIMScheduler:
-            return sched.coefficient_table(eta) if eta != 0.0 else None
-        if type(sched) in (DDPMScheduler, DPMSolverMultistepScheduler):
-            return sched.coefficient_table()
-        return None
-
+    # ---- stochastic samplers (DDIM with eta, DDPM, SDE-DPM-Solver++) --------------------------------------------------
     def _draw_seed(self, scheds, eta: float, generator) -> Optional[int]:
         """ONE int64 per sampling call that keys the noise of every step (``ur_sde_update``, ``ops.sampler_noise``,
         ``schedulers.philox_normal``), drawn from ``generator`` (the global generator if None) -- the package's own stream, not
         ``torch.randn``'s: the same ``manual_seed`` gives the same images, a second call on the same generator object other
-        ones.  None, and nothing drawn, when no scheduler of the call has a noise term."""
-        noisy = False
-        for s in scheds:
-            tab = self._sde_table(s, eta)
-            noisy = noisy or (tab is not None and bool((tab[:, 3] != 0).any()))
-        if not noisy:
+        ones.  None, and nothing drawn, when no scheduler of the call has a noise term (a foreign scheduler has none here)."""
+        plans = [device_plan(s, eta) for s in scheds]
+        if not any(p is not None and p.noisy for p in plans):
             return None
         if isinstance(generator, (list, tuple)):
             generator = generator[0]
@@ -463,31 +492,6 @@ class UniRendererPipeline:
         from .schedulers import philox_normal
 
         return philox_normal(seed, i, shape).to(device)
-
-    @staticmethod
-    def _step_kwargs(sched, eta: float, noise) -> Dict[str, Any]:
-        """ref ``prepare_extra_step_kwargs``: eta goes to the DDIM scheduler only; the noise to the classes that take it."""
-        from .schedulers import DDIMScheduler, DDPMScheduler, DPMSolverMultistepScheduler
-
-        kw: Dict[str, Any] = {}
-        if type(sched) is DDIMScheduler and eta != 0.0:
-            kw["eta"] = eta
-        if noise is not None and type(sched) in (DDIMScheduler, DDPMScheduler, DPMSolverMultistepScheduler):
-            kw["variance_noise"] = noise
-        return kw
-
-    @staticmethod
-    def _ddim_tables(sched, timesteps):
-        """[n, 4] fp32 rows sqrt(a_t), sqrt(1-a_t), sqrt(a_prev), sqrt(1-a_prev) -- the same fp32 torch expressions as
-        DDIMScheduler.step -- and the timestep values as floats."""
-        rows = []
-        ts = [int(t) for t in timesteps.cpu().tolist()]
-        for t in ts:
-            prev_t = t - sched.num_train_timesteps // (sched.num_inference_steps or sched.num_train_timesteps)
-            a_t = sched._alpha(t, "cpu")
-            a_prev = sched._alpha(prev_t, "cpu") if prev_t >= 0 else sched.final_alpha_cumprod.to("cpu")
-            rows.append(torch.stack([a_t.sqrt(), (1 - a_t).sqrt(), a_prev.sqrt(), (1 - a_prev).sqrt()]).float())
-        return torch.stack(rows), torch.tensor(ts, dtype=torch.float32)
 
     def _graph_key(self, x_img, ehs, run_decoder, cond_scale: float = 1.0):
         """Everything a captured step bakes in besides the weights: shapes, dtype, executor, conditioning scale, the
@@ -543,80 +547,46 @@ class UniRendererPipeline:
         key, g = self._graph_for(x_img, cond28, ehs, run_decoder, cond_scale)
         t0 = float(timesteps[0])
         g.load_inputs(x_img, cond28, ehs, 0.0 if run_decoder else t0, t0 if run_decoder else 0.0)
-        from .schedulers import UniPCMultistepScheduler
-
-        unipc = type(sched) is UniPCMultistepScheduler
-        sde_table = self._sde_table(sched, eta)
-        sde = sde_table is not None
-        if unipc:
-            coef, tvals = sched.coefficient_table(), timesteps.detach().cpu().to(torch.float32)
-        elif sde:
-            coef, tvals = sde_table, timesteps.detach().cpu().to(torch.float32)
-        else:
-            coef, tvals = self._ddim_tables(sched, timesteps)
-        kind = "unipc" if unipc else ("sde-" + type(sched).__name__ if sde else "ddim")
-        skey = key + (() if views is None else (("views",) + tuple(views),)) + (n, lat_dtype, guidance, self.precompute_time_tables, kind)
+        plan = device_plan(sched, eta)
+        skey = key + (() if views is None else (("views",) + tuple(views),)) + (n, lat_dtype, guidance, self.precompute_time_tables, plan.kind)
         st = self._sample_graphs.get(skey)
         if st is None:
             dev = x_img.device
             evolving = g.cond[:, 4:] if run_decoder else g.x_t
             mshape = (nb,) + tuple(evolving.shape[1:])
-            st = dict(step=torch.zeros(1, dtype=torch.int32, device=dev), coef=torch.zeros(n, coef.shape[1], device=dev),
-                      tvals=torch.zeros(n, device=dev),
-                      master=torch.zeros(mshape, dtype=torch.float32, device=dev),
-                      round_master=lat_dtype != torch.float32)
-            if unipc:  # corrected sample L and the two previous predictions (ur_unipc_update)
-                st["last"] = torch.zeros(mshape, dtype=torch.float32, device=dev)
-                st["hist"] = torch.zeros((2,) + mshape, dtype=torch.float32, device=dev)
-            if sde:  # the previous prediction and the noise key (ur_sde_update)
-                st["hist"] = torch.zeros(mshape, dtype=torch.float32, device=dev)
-                st["seed"] = torch.zeros(1, dtype=torch.int64, device=dev)
+            sampler = _SamplerState(plan.kind, n, plan.coef.shape[1])
+            sampler.allocate(mshape, dev, round_master=lat_dtype != torch.float32)
+            st = dict(sampler=sampler)
             if views is not None:  # the blended global latent (ur_view_blend writes it on every step)
                 st["global"] = torch.zeros((nb // views.num_views, mshape[1], views.height, views.width), dtype=torch.float32, device=dev)
 
             def update(pred_nhwc, c0, lat, cfg_channels):
-                if sde:
-                    ops.sde_update(pred_nhwc, c0, lat, st["coef"], st["step"], n, st["seed"], st["master"], st["hist"],
-                                   round_master=st["round_master"], guidance=guidance, cfg_channels=cfg_channels)
-                elif unipc:
-                    ops.unipc_update(pred_nhwc, c0, lat, st["coef"], st["step"], n, st["last"], st["master"], st["hist"],
-                                     round_master=st["round_master"], guidance=guidance, cfg_channels=cfg_channels)
-                else:
-                    ops.ddim_update(pred_nhwc, c0, lat, st["coef"], st["step"], n, master=st["master"],
-                                    round_master=st["round_master"], guidance=guidance, cfg_channels=cfg_channels)
+                sampler.update(pred_nhwc, c0, lat, guidance, cfg_channels)
                 if views is not None:  # every view <- the mean of the views that cover each of its pixels
-                    ops.view_blend(st["master"], lat, st["global"], views, halves=2 if cfg else 1, round_master=st["round_master"])
+                    ops.view_blend(sampler.master, lat, st["global"], views, halves=2 if cfg else 1, round_master=sampler.round_master)
 
             def post(out):
                 if run_decoder:  # the material group is channels 4..7 of the 28
                     update(out["attr_pred"].permute(0, 2, 3, 1), 4, g.cond[:, 4:], 4)
-                    ops.sampler_advance(st["step"], st["tvals"], n, g.t_attr)
+                    ops.sampler_advance(sampler.step, sampler.tvals, n, g.t_attr)
                 else:
                     update(out["img_pred"].permute(0, 2, 3, 1), 0, g.x_t, g.x_t.shape[1])
-                    ops.sampler_advance(st["step"], st["tvals"], n, g.t_img)
+                    ops.sampler_advance(sampler.step, sampler.tvals, n, g.t_img)
 
             if isinstance(g, GraphedHoistedStep) and self.precompute_time_tables:
                 # the time projections of all n steps once per call (they depend on the timestep only); the step graph picks
                 # its rows with the device-side step counter
-                st["tgraph"], (tab1, tab3) = g.capture_time_tables(st["tvals"])
-                st["graph"], st["out"] = g.capture_with(post, tables=(tab1, tab3, st["step"]))
+                st["tgraph"], (tab1, tab3) = g.capture_time_tables(sampler.tvals)
+                st["graph"], st["out"] = g.capture_with(post, tables=(tab1, tab3, sampler.step))
             else:
                 st["graph"], st["out"] = g.capture_with(post)
             self._sample_graphs[skey] = st
             g.load_inputs(x_img, cond28, ehs, 0.0 if run_decoder else t0, t0 if run_decoder else 0.0)  # capture ran no kernel, but be explicit
-        st["step"].zero_()
-        st["coef"].copy_(coef)
-        st["tvals"].copy_(tvals)
-        st["master"].copy_((cond28[:nb, 4:] if run_decoder else x_img[:nb]))  # the caller's latents at their own precision
-        if unipc:
-            st["last"].copy_(st["master"])  # L_0 = the initial sample
-            st["hist"].zero_()
-        if sde:
-            st["hist"].zero_()
-            st["seed"].fill_(0 if seed is None else seed)
+        sampler = st["sampler"]
+        sampler.reset((cond28[:nb, 4:] if run_decoder else x_img[:nb]), seed, plan)  # the caller's latents at their own precision
         hoisted = isinstance(g, GraphedHoistedStep)
         if st.get("tgraph") is not None:
-            st["tgraph"].replay()  # time projections of every step of this call (st["tvals"] was written above)
+            st["tgraph"].replay()  # time projections of every step of this call (the reset above wrote its timesteps)
         if hoisted:
             g.begin()  # the loop-invariant half, once per call
         for _ in range(n):
@@ -624,7 +594,7 @@ class UniRendererPipeline:
                 g.pro.replay()
             st["graph"].replay()
         # a COPY: ``master`` is this sampling graph's static buffer and the next call with the same shapes overwrites it
-        return st["master" if views is None else "global"].to(lat_dtype, copy=True)
+        return (sampler.master if views is None else st["global"]).to(lat_dtype, copy=True)
 
     def _step(self, x_img, cond28, ehs, t_img, t_attr, run_decoder: bool, cond_scale: float = 1.0, sig=None, first: bool = True):
         """One step of a sampling loop.  ``first``: the first step of a loop (the hoisted executor runs its prologue on the
@@ -659,6 +629,72 @@ class UniRendererPipeline:
             full[idx] = o  # the executor's output buffer is static: copy before the next chunk runs
         return {name: full}
 
+    def _sample(self, *, fixed, lat, scheds, guided, input_sched, run_decoder: bool, timesteps, num_inference_steps,
+                prompt_embeds, geo, cond_scale: float, eta: float, generator, callback=None):
+        """The sampling loop of both directions.  ``fixed``: the clean inputs as global tensors -- inverse (``run_decoder``): the
+        image and mask latents, whose timestep is the constant 0; rendering: the 28 attribute channels.  ``lat``: the evolving
+        latent groups (global, initial noise), ``scheds`` their schedulers, ``guided`` which of them classifier-free guidance
+        combines (the others keep the cond half; inverse: ``material`` only, ref 2697-2721; rendering: the image, ref
+        1642-1644).  ``input_sched`` scales the evolving input of every step; the on-device loop needs it and ``scheds`` on one
+        common schedule.  Returns the final groups (global under MultiDiffusion ``geo``)."""
+        device, cfg = prompt_embeds.device, self.do_classifier_free_guidance
+        widths = [t.shape[1] for t in lat]
+        cat = lambda parts: torch.cat(parts, dim=1) if len(parts) > 1 else parts[0]
+        glob = None
+        if geo is not None:  # the global tensors are cut into views ONCE per call; view v of sample n is batch row n * V + v
+            glob = cat(lat).float()
+            fixed, lat = [gather_views(t, geo) for t in fixed], [gather_views(t, geo) for t in lat]
+            prompt_embeds = prompt_embeds.repeat_interleave(geo.num_views, dim=0)
+        dup = (lambda t: torch.cat([t, t])) if cfg else (lambda t: t)
+        fixed = [dup(self.scheduler_img.scale_model_input(t, 0)) for t in fixed]
+
+        def inputs(x):  # (x_img, cond28) of a step: inverse = mask latent first, 4 + 6*4 = 28 channels
+            return (fixed[0], torch.cat((fixed[1].to(x.dtype), x), dim=1)) if run_decoder else (x, fixed[0])
+
+        seed = self._draw_seed(scheds, eta, generator)  # after the initial latents, in both loops: same generator state
+        with self.progress_bar(total=num_inference_steps) as bar:
+            if self._fusable([input_sched] + scheds, device, cond_scale, callback, eta):
+                x = cat([dup(t) for t in lat])
+                fin = self._fused_loop(*inputs(x), prompt_embeds, timesteps, scheds[0], run_decoder=run_decoder, lat_dtype=x.dtype,
+                                       guidance=(float(self.guidance_scale) if cfg else None), cond_scale=cond_scale, eta=eta,
+                                       seed=seed, views=geo)
+                return [f.to(t.dtype) for f, t in zip(fin.split(widths, dim=1), lat)]  # ``fin`` is the global latent already
+            sig = self._weights_signature()  # once per call, not per step
+            seed_dev = torch.tensor([seed], dtype=torch.int64, device=device) if seed is not None else None
+            chunks, chunk_fixed = (self._view_chunks(lat[0].shape[0], cfg, device) if geo is not None else None), {}
+            plans = [device_plan(s, eta) for s in scheds]
+            # the clean side's timestep is the constant 0 (ref 2476 / 1455): hand the hoisted executor the SAME tensor object on
+            # every step -- it re-runs its prologue when a fixed input changes identity (graph.GraphedHoistedStep.step)
+            t_zero = torch.zeros_like(timesteps)[0] if len(timesteps) else None
+            for i, t in enumerate(timesteps):
+                x_img, cond28 = inputs(input_sched.scale_model_input(cat([dup(v) for v in lat]), t))
+                t_img, t_attr = (t_zero, t) if run_decoder else (t, t_zero)
+                if chunks is None:
+                    out = self._step(x_img, cond28, prompt_embeds, t_img, t_attr, run_decoder=run_decoder, cond_scale=cond_scale,
+                                     sig=sig, first=(i == 0))
+                else:
+                    out = self._step_chunked(chunks, chunk_fixed, x_img, cond28, prompt_embeds, t_img, t_attr,
+                                             run_decoder=run_decoder, cond_scale=cond_scale, sig=sig, first=(i == 0))
+                preds = (out["attr_pred"][:, 4:] if run_decoder else out["img_pred"]).split(widths, dim=1)  # drop the mask group (ref 2691)
+                # the groups are ONE latent to the noise stream, as in the fused loop (MultiDiffusion: over the [N * V, ...] view
+                # batch, so overlapping views draw independent noise)
+                noise = self._step_noise(seed, seed_dev, i, (lat[0].shape[0], sum(widths)) + tuple(lat[0].shape[2:]), device)
+                noises = [None] * len(lat) if noise is None else noise.split(widths, dim=1)
+                for k, (pred, sch, plan) in enumerate(zip(preds, scheds, plans)):
+                    if cfg:
+                        p_cond, p_uncond = pred.chunk(2)  # chunk order exactly as the reference reads it
+                        pred = p_uncond + self.guidance_scale * (p_cond - p_uncond) if guided[k] else p_cond
+                    kw_step = plan.step_kwargs(eta, noises[k]) if plan is not None else {}
+                    lat[k] = sch.step(pred, t, lat[k], return_dict=False, **kw_step)[0]
+                if geo is not None:  # where the fused loop's graph has ur_view_blend
+                    lat, glob = self._blend_views(lat, geo)
+                if callback is not None:
+                    callback(self, i, t, {"latents": lat[0]})
+                bar.update()
+        if glob is not None:  # the step-by-step MultiDiffusion loop: the results are the global latents
+            lat = [g_.to(t.dtype) for g_, t in zip(glob.split(widths, dim=1), lat)]
+        return lat
+
     # =====================================================================================================
     @torch.no_grad()
     def real_image2mask_3mod_albedo(
@@ -691,8 +727,7 @@ class UniRendererPipeline:
         timesteps_attr, num_inference_steps = retrieve_timesteps(self.scheduler_attr, num_inference_steps, device)
         for n in ATTR_GROUPS:
             retrieve_timesteps(getattr(self, f"scheduler_{n}"), num_inference_steps, device)
-        self._num_timesteps = len(timesteps_attr)
-        timesteps_img = torch.zeros_like(timesteps_attr)  # the image latent is clean: t_img = 0 (ref 2476)
+        self._num_timesteps = len(timesteps_attr)  # the image latent is clean: t_img = 0 (ref 2476)
 
         if image_latents is None:
             if not torch.is_tensor(image):
@@ -723,71 +758,13 @@ class UniRendererPipeline:
         nlat = self.unet.config.in_channels
         lat = {n: self.prepare_latents(total, nlat, height, width, prompt_embeds.dtype,
                                        device, generator, latents) for n in ATTR_GROUPS}
-        cfg = self.do_classifier_free_guidance
-        glob = None
-        if geo is not None:  # the global tensors are cut into views ONCE per call; view v of sample n is batch row n * V + v
-            glob = torch.cat([lat[n] for n in ATTR_GROUPS], dim=1).float()
-            image_latents, mask_latents = gather_views(image_latents, geo), gather_views(mask_latents, geo)
-            lat = {n: gather_views(lat[n], geo) for n in ATTR_GROUPS}
-            prompt_embeds = prompt_embeds.repeat_interleave(geo.num_views, dim=0)
-        dup = (lambda t: torch.cat([t, t])) if cfg else (lambda t: t)
-        x_img = self.scheduler_img.scale_model_input(dup(image_latents), 0)
-        x_mask = self.scheduler_img.scale_model_input(dup(mask_latents), 0)
-        cond_scale = float(controlnet_conditioning_scale)
-
-        group_scheds = [getattr(self, f"scheduler_{n}") for n in ATTR_GROUPS]
-        eta = float(eta)
-        seed = self._draw_seed(group_scheds, eta, generator)  # after the initial latents, in both loops: same generator state
-        if self._fusable([self.scheduler_attr] + group_scheds, device, cond_scale, callback_on_step_end):
-            cat = torch.cat([dup(lat[n]) for n in ATTR_GROUPS], dim=1)
-            cond28 = torch.cat((x_mask.to(cat.dtype), cat), dim=1)
-            fin = self._fused_loop(x_img, cond28, prompt_embeds, timesteps_attr, group_scheds[0], run_decoder=True,
-                                   lat_dtype=cat.dtype, guidance=(float(self.guidance_scale) if cfg else None),
-                                   cond_scale=cond_scale, eta=eta, seed=seed, views=geo)
-            lat = {n: fin[:, 4 * k:4 * k + 4].to(lat[n].dtype) for k, n in enumerate(ATTR_GROUPS)}
-            glob = None  # ``fin`` is the global latent already
-            timesteps_img = timesteps_attr = []  # loop below is skipped
-        sig = self._weights_signature() if len(timesteps_attr) else None  # once per call, not per step
-        seed_dev = torch.tensor([seed], dtype=torch.int64, device=device) if seed is not None and len(timesteps_attr) else None
-        chunks, chunk_fixed = (self._view_chunks(lat["material"].shape[0], cfg, device) if geo is not None and len(timesteps_attr) else None), {}
-        with self.progress_bar(total=num_inference_steps) as bar:
-            # the clean image latent's timestep is the constant 0 (ref 2476): hand the hoisted executor the SAME tensor object on every
-            # step -- it re-runs its prologue when a fixed input changes identity (graph.GraphedHoistedStep.step), and the per-step
-            # elements of `timesteps_img` are distinct views
-            t_img_fixed = timesteps_img[0] if len(timesteps_img) else None
-            for i, (_, t_attr) in enumerate(zip(timesteps_img, timesteps_attr)):
-                t_img = t_img_fixed
-                cat = torch.cat([dup(lat[n]) for n in ATTR_GROUPS], dim=1)
-                cat = self.scheduler_attr.scale_model_input(cat, t_attr)
-                cond28 = torch.cat((x_mask.to(cat.dtype), cat), dim=1)  # mask latent first: 4 + 6*4 = 28 channels
-                if chunks is None:
-                    out = self._step(x_img, cond28, prompt_embeds, t_img, t_attr, run_decoder=True, cond_scale=cond_scale, sig=sig,
-                                     first=(i == 0))
-                else:
-                    out = self._step_chunked(chunks, chunk_fixed, x_img, cond28, prompt_embeds, t_img, t_attr, run_decoder=True,
-                                             cond_scale=cond_scale, sig=sig, first=(i == 0))
-                label_pred = out["attr_pred"][:, 4:]  # drop the mask group (ref 2691)
-                # the six groups are ONE 24-channel latent to the noise stream, as in the fused loop (MultiDiffusion: over the
-                # [N * V, ...] view batch, so overlapping views draw independent noise)
-                nshape = (total, 4 * len(ATTR_GROUPS), h8, w8) if geo is None else (total * geo.num_views, 4 * len(ATTR_GROUPS), geo.wh, geo.ww)
-                noise = self._step_noise(seed, seed_dev, i, nshape, device)
-                for k, n in enumerate(ATTR_GROUPS):
-                    pred = label_pred[:, 4 * k:4 * k + 4]
-                    if cfg:
-                        # chunk order exactly as the reference reads it (2697-2721)
-                        p_cond, p_uncond = pred.chunk(2)
-                        pred = p_uncond + self.guidance_scale * (p_cond - p_uncond) if n == "material" else p_cond
-                    sch = getattr(self, f"scheduler_{n}")
-                    kw_step = self._step_kwargs(sch, eta, None if noise is None else noise[:, 4 * k:4 * k + 4])
-                    lat[n] = sch.step(pred, t_attr, lat[n], return_dict=False, **kw_step)[0]
-                if geo is not None:  # where the fused loop's graph has ur_view_blend
-                    parts, glob = self._blend_views([lat[n] for n in ATTR_GROUPS], geo)
-                    lat = dict(zip(ATTR_GROUPS, parts))
-                if callback_on_step_end is not None:
-                    callback_on_step_end(self, i, t_attr, {"latents": lat["material"]})
-                bar.update()
-        if glob is not None:  # the step-by-step MultiDiffusion loop: the results are the global latents
-            lat = {n: glob[:, 4 * k:4 * k + 4].to(lat[n].dtype) for k, n in enumerate(ATTR_GROUPS)}
+        fin = self._sample(fixed=[image_latents, mask_latents], lat=[lat[n] for n in ATTR_GROUPS],
+                           scheds=[getattr(self, f"scheduler_{n}") for n in ATTR_GROUPS],
+                           guided=[n == "material" for n in ATTR_GROUPS], input_sched=self.scheduler_attr, run_decoder=True,
+                           timesteps=timesteps_attr, num_inference_steps=num_inference_steps, prompt_embeds=prompt_embeds, geo=geo,
+                           cond_scale=float(controlnet_conditioning_scale), eta=float(eta), generator=generator,
+                           callback=callback_on_step_end)
+        lat = dict(zip(ATTR_GROUPS, fin))
         if output_type == "latent":
             return tuple(lat[n] for n in ATTR_GROUPS)
         # the five image groups (ref 2755-2769: five vae.decode calls) decoded as ONE batch
@@ -825,8 +802,7 @@ class UniRendererPipeline:
             prompt, device, num_images_per_prompt, self.do_classifier_free_guidance, negative_prompt,
             prompt_embeds=prompt_embeds, negative_prompt_embeds=negative_prompt_embeds)
         timesteps, num_inference_steps = retrieve_timesteps(self.scheduler_img, num_inference_steps, device)
-        self._num_timesteps = len(timesteps)
-        timesteps_attr = torch.zeros_like(timesteps)  # attributes are clean (ref 1455)
+        self._num_timesteps = len(timesteps)  # the attributes are clean: t_attr = 0 (ref 1455)
         if attr_latents is None:
             bs = batch_size * num_images_per_prompt
             prep = lambda im: self.prepare_image(im, width, height, bs, num_images_per_prompt, device, self.controlnet.dtype)
@@ -846,49 +822,10 @@ class UniRendererPipeline:
         self._prepare_ip_adapter(ip_adapter_image, device, batch_size, num_images_per_prompt, views=geo.num_views if geo else 1)
         height, width = height or h8 * self.vae_scale_factor, width or w8 * self.vae_scale_factor
         latents_img = self.prepare_latents(batch_size, 4, height, width, prompt_embeds.dtype, device, generator, latents)
-        cfg = self.do_classifier_free_guidance
-        glob = None
-        if geo is not None:
-            glob = latents_img.float()
-            attr_latents, latents_img = gather_views(attr_latents, geo), gather_views(latents_img, geo)
-            prompt_embeds = prompt_embeds.repeat_interleave(geo.num_views, dim=0)
-        dup = (lambda t: torch.cat([t, t])) if cfg else (lambda t: t)
-        cond28 = dup(self.scheduler_img.scale_model_input(attr_latents, 0))
-        eta = float(eta)
-        seed = self._draw_seed([self.scheduler_img], eta, generator)
-        if self._fusable([self.scheduler_img], device, float(controlnet_conditioning_scale), None):
-            latents_img = self._fused_loop(dup(latents_img), cond28, prompt_embeds, timesteps, self.scheduler_img,
-                                           run_decoder=False, lat_dtype=latents_img.dtype,
-                                           guidance=(float(self.guidance_scale) if cfg else None),
-                                           cond_scale=float(controlnet_conditioning_scale), eta=eta, seed=seed, views=geo)
-            glob = None  # the fused loop returned the global latent
-            timesteps = timesteps[:0]  # loop below is skipped
-        sig = self._weights_signature() if len(timesteps) else None
-        seed_dev = torch.tensor([seed], dtype=torch.int64, device=device) if seed is not None and len(timesteps) else None
-        chunks, chunk_fixed = (self._view_chunks(latents_img.shape[0], cfg, device) if geo is not None and len(timesteps) else None), {}
-        with self.progress_bar(total=num_inference_steps) as bar:
-            t_attr_fixed = timesteps_attr[0] if len(timesteps) else None  # clean attributes: the constant 0, one object (see above)
-            for i in range(len(timesteps)):
-                t_img, t_attr = timesteps[i], t_attr_fixed
-                x = self.scheduler_img.scale_model_input(dup(latents_img), t_img)
-                if chunks is None:
-                    out = self._step(x, cond28, prompt_embeds, t_img, t_attr, run_decoder=False,
-                                     cond_scale=float(controlnet_conditioning_scale), sig=sig, first=(i == 0))
-                else:
-                    out = self._step_chunked(chunks, chunk_fixed, x, cond28, prompt_embeds, t_img, t_attr, run_decoder=False,
-                                             cond_scale=float(controlnet_conditioning_scale), sig=sig, first=(i == 0))
-                img_pred = out["img_pred"]
-                if cfg:
-                    p_cond, p_uncond = img_pred.chunk(2)  # ref 1642-1644
-                    img_pred = p_uncond + self.guidance_scale * (p_cond - p_uncond)
-                noise = self._step_noise(seed, seed_dev, i, tuple(latents_img.shape), device)
-                latents_img = self.scheduler_img.step(img_pred, t_img, latents_img, return_dict=False,
-                                                      **self._step_kwargs(self.scheduler_img, eta, noise))[0]
-                if geo is not None:
-                    (latents_img,), glob = self._blend_views([latents_img], geo)
-                bar.update()
-        if glob is not None:
-            latents_img = glob.to(latents_img.dtype)
+        (latents_img,) = self._sample(fixed=[attr_latents], lat=[latents_img], scheds=[self.scheduler_img], guided=[True],
+                                      input_sched=self.scheduler_img, run_decoder=False, timesteps=timesteps,
+                                      num_inference_steps=num_inference_steps, prompt_embeds=prompt_embeds, geo=geo,
+                                      cond_scale=float(controlnet_conditioning_scale), eta=float(eta), generator=generator)
         if output_type == "latent":
             return latents_img
         return self._postprocess(self._vae_decode(latents_img, generator), output_type)

@@ -10,7 +10,9 @@ diffusers itself is unpinned): ``DDIMScheduler`` (eta = 0 and eta != 0) with the
 ``DPMSolverMultistepScheduler`` (DPM-Solver++ 1 / 2M and its SDE variant).  All of them run inside the fused sampling
 loop (one update kernel per step: ``ur_ddim_update``, ``ur_unipc_update``, ``ur_sde_update``); an object of another
 class that follows the protocol with ``init_noise_sigma == 1`` takes the step-by-step loop.  The Euler / Heun / PNDM
-families are refused by name (``NotImplementedError``).
+families are refused by name (``NotImplementedError``).  ``device_plan(scheduler, eta)`` is the one description of a
+scheduler the pipeline reads: which update kernel, its coefficient table, the timesteps, whether it draws noise, and the
+keywords of its ``step``.
 
 Noise: a stochastic sampler inside the pipeline draws from the package's own counter-based stream (``philox_normal``
 here, ``ops.sampler_noise`` / ``ur_sde_update`` on the device), keyed by ONE int64 drawn from the caller's generator
@@ -19,14 +21,85 @@ per call -- not from ``torch.randn``'s stream.  A ``step`` called directly takes
 """
 from __future__ import annotations
 
+from dataclasses import dataclass
 from typing import Optional, Tuple, Union
 
 import torch
 
 
-class DDIMScheduler:
+def _betas(beta_schedule: str, beta_start: float, beta_end: float, n: int) -> torch.Tensor:
+    if beta_schedule == "scaled_linear":
+        return torch.linspace(beta_start ** 0.5, beta_end ** 0.5, n, dtype=torch.float32) ** 2
+    if beta_schedule == "linear":
+        return torch.linspace(beta_start, beta_end, n, dtype=torch.float32)
+    raise NotImplementedError(f"beta_schedule {beta_schedule!r}: scaled_linear and linear are implemented")
+
+
+def _config_of(config):
+    c = dict(getattr(config, "config", config))
+    return {k: v for k, v in c.items() if not k.startswith("_")}
+
+
+class _Scheduler:
+    """What the four schedulers share: the variance-preserving protocol constants, ``add_noise``, the eps -> x0 conversion,
+    the timestep grid of the multistep solvers and ``from_config``."""
+
     order = 1
     init_noise_sigma = 1.0
+    _config_drop: Tuple[str, ...] = ()  # config keys the constructor does not take
+
+    @classmethod
+    def from_config(cls, config, **overrides):
+        """``config``: a dict (the SD-1.x scheduler config) or a scheduler object of any class of this module."""
+        c = {k: v for k, v in _config_of(config).items() if k not in cls._config_drop}
+        c.update(overrides)
+        return cls(**c)
+
+    def scale_model_input(self, sample: torch.Tensor, timestep=None) -> torch.Tensor:
+        return sample
+
+    def add_noise(self, original: torch.Tensor, noise: torch.Tensor, timesteps: torch.Tensor) -> torch.Tensor:
+        a = self.alphas_cumprod.to(original.device)[timesteps.long()].to(original.dtype)
+        while a.dim() < original.dim():
+            a = a[..., None]
+        return a.sqrt() * original + (1 - a).sqrt() * noise
+
+    def _to_x0(self, model_output, sample, alpha, sigma):
+        """The model's output as an x0 prediction: itself, or (x - sigma eps) / alpha for an eps-predicting model, in fp32
+        (float64 for a float64 sample)."""
+        if self.prediction_type == "sample":
+            return model_output
+        cd = torch.float64 if sample.dtype == torch.float64 else torch.float32
+        return (sample.to(cd) - sigma * model_output.to(cd)) / alpha
+
+    @staticmethod
+    def _alpha_sigma(sigma):
+        alpha_t = 1.0 / ((sigma ** 2 + 1.0) ** 0.5)
+        return alpha_t, sigma * alpha_t
+
+    def _index_for(self, timestep):
+        t = int(torch.as_tensor(timestep).flatten()[0].item())
+        idx = (self.timesteps.cpu() == t).nonzero()
+        return int(idx[1 if len(idx) > 1 else 0]) if len(idx) else len(self.timesteps) - 1
+
+    def _multistep_timesteps(self, num_inference_steps: int):
+        """The int64 numpy grid of UniPC and DPM-Solver++: ``num_inference_steps + 1`` points, the last (t = 0) dropped."""
+        import numpy as np
+
+        n_train, sp = self.num_train_timesteps, self.config["timestep_spacing"]
+        if sp == "linspace":
+            return np.linspace(0, n_train - 1, num_inference_steps + 1).round()[::-1][:-1].copy().astype(np.int64)
+        if sp == "leading":
+            ratio = n_train // (num_inference_steps + 1)
+            ts = (np.arange(0, num_inference_steps + 1) * ratio).round()[::-1][:-1].copy().astype(np.int64)
+            return ts + self.config["steps_offset"]
+        if sp == "trailing":
+            return (np.arange(n_train, 0, -n_train / num_inference_steps).round() - 1).astype(np.int64)
+        raise ValueError(sp)
+
+
+class DDIMScheduler(_Scheduler):
+    _config_drop = ("beta_schedule", "clip_sample")  # constants of this class that its config records
 
     def __init__(self, num_train_timesteps: int = 1000, beta_start: float = 0.00085, beta_end: float = 0.012,
                  prediction_type: str = "sample", steps_offset: int = 1, set_alpha_to_one: bool = False):
@@ -38,6 +111,7 @@ class DDIMScheduler:
         self.num_train_timesteps = num_train_timesteps
         self.prediction_type = prediction_type
         self.steps_offset = steps_offset
+        # float64 betas, alphas_cumprod rounded to fp32 (the other classes build theirs in fp32: _betas)
         betas = torch.linspace(beta_start ** 0.5, beta_end ** 0.5, num_train_timesteps, dtype=torch.float64) ** 2
         self.alphas_cumprod = torch.cumprod(1.0 - betas, dim=0).float()
         self.final_alpha_cumprod = torch.tensor(1.0) if set_alpha_to_one else self.alphas_cumprod[0]
@@ -49,9 +123,6 @@ class DDIMScheduler:
         ratio = self.num_train_timesteps // num_inference_steps
         ts = (torch.arange(0, num_inference_steps) * ratio).flip(0) + self.steps_offset
         self.timesteps = ts.clamp_max(self.num_train_timesteps - 1).to(device)
-
-    def scale_model_input(self, sample: torch.Tensor, timestep=None) -> torch.Tensor:
-        return sample
 
     def _alpha(self, t, device):
         t = torch.as_tensor(t, device="cpu").long().clamp(0, self.num_train_timesteps - 1)
@@ -73,6 +144,17 @@ class DDIMScheduler:
         p0 = max(1 - a_prev - sigma * sigma, 0.0) ** 0.5 / (1 - a_t) ** 0.5
         return (p0, a_prev ** 0.5 - a_t ** 0.5 * p0, 0.0, sigma)
 
+    def _sqrt_rows(self) -> torch.Tensor:
+        """[n, 4] fp32 rows sqrt(a_t), sqrt(1 - a_t), sqrt(a_prev), sqrt(1 - a_prev) over ``timesteps``: what ``ur_ddim_update``
+        consumes at ``eta == 0`` -- the same fp32 torch expressions as ``step``."""
+        rows = []
+        for t in self.timesteps.cpu().tolist():
+            prev_t = int(t) - self.num_train_timesteps // (self.num_inference_steps or self.num_train_timesteps)
+            a_t = self._alpha(int(t), "cpu")
+            a_prev = self._alpha(prev_t, "cpu") if prev_t >= 0 else self.final_alpha_cumprod.to("cpu")
+            rows.append(torch.stack([a_t.sqrt(), (1 - a_t).sqrt(), a_prev.sqrt(), (1 - a_prev).sqrt()]).float())
+        return torch.stack(rows)
+
     def coefficient_table(self, eta: float = 0.0) -> torch.Tensor:
         """[n, 4] fp32 rows (p0, p1, p2, pn) over ``timesteps``: what ``ur_sde_update`` consumes and what ``step`` with
         ``eta != 0`` evaluates (p2 = 0: DDIM is a one-step method).  The fused loop runs ``eta == 0`` on ``ur_ddim_update``."""
@@ -88,7 +170,9 @@ class DDIMScheduler:
         if eta != 0.0:
             if use_clipped_model_output:
                 raise NotImplementedError("DDIMScheduler: use_clipped_model_output")
-            prev = _linear_step(self._row64(t, eta), self._to_x0(model_output, t, sample), sample, None, generator, variance_noise)
+            a_t = self._alphas_at(t)[0]
+            m = self._to_x0(model_output, sample, a_t ** 0.5, (1 - a_t) ** 0.5)
+            prev = _linear_step(self._row64(t, eta), m, sample, None, generator, variance_noise)
             return (prev,) if not return_dict else {"prev_sample": prev}
         prev_t = t - self.num_train_timesteps // (self.num_inference_steps or self.num_train_timesteps)
         a_t = self._alpha(t, sample.device)
@@ -105,19 +189,6 @@ class DDIMScheduler:
         prev = prev.to(sample.dtype)
         return (prev,) if not return_dict else {"prev_sample": prev}
 
-    def _to_x0(self, model_output, t: int, sample):
-        if self.prediction_type == "sample":
-            return model_output
-        cd = torch.float64 if sample.dtype == torch.float64 else torch.float32
-        a_t = self._alphas_at(t)[0]
-        return (sample.to(cd) - (1 - a_t) ** 0.5 * model_output.to(cd)) / a_t ** 0.5
-
-    def add_noise(self, original: torch.Tensor, noise: torch.Tensor, timesteps: torch.Tensor) -> torch.Tensor:
-        a = self.alphas_cumprod.to(original.device)[timesteps.long()].to(original.dtype)
-        while a.dim() < original.dim():
-            a = a[..., None]
-        return a.sqrt() * original + (1 - a).sqrt() * noise
-
 
 def retrieve_timesteps(scheduler, num_inference_steps: Optional[int] = None, device=None, timesteps=None, **kw
                        ) -> Tuple[torch.Tensor, int]:
@@ -129,7 +200,7 @@ def retrieve_timesteps(scheduler, num_inference_steps: Optional[int] = None, dev
     return scheduler.timesteps, num_inference_steps
 
 
-class UniPCMultistepScheduler:
+class UniPCMultistepScheduler(_Scheduler):
     """UniPC (Zhao et al. 2023) multistep predictor-corrector, restated from the published algorithm as diffusers 0.24's
     ``UniPCMultistepScheduler`` implements it (the scheduler eval/test_real.py:485-492 attaches eight times and runs for
     20 steps): B(h) variant ``bh2``, data prediction (``predict_x0=True``), ``solver_order`` 2 with first-order warm-up
@@ -143,9 +214,6 @@ class UniPCMultistepScheduler:
     scalar weights; ``coefficient_table()`` exposes them so the pipeline can run the update as one HIP kernel
     (``ur_unipc_update``) inside the step graph."""
 
-    init_noise_sigma = 1.0
-    order = 1
-
     def __init__(self, num_train_timesteps: int = 1000, beta_start: float = 0.00085, beta_end: float = 0.012,
                  beta_schedule: str = "scaled_linear", solver_order: int = 2, prediction_type: str = "sample",
                  predict_x0: bool = True, solver_type: str = "bh2", lower_order_final: bool = True,
@@ -154,12 +222,7 @@ class UniPCMultistepScheduler:
             raise NotImplementedError("UniPC: solver_order 1 / 2, predict_x0, bh2 (the diffusers defaults) are implemented")
         if prediction_type not in ("sample", "epsilon"):
             raise ValueError(prediction_type)
-        if beta_schedule == "scaled_linear":
-            betas = torch.linspace(beta_start ** 0.5, beta_end ** 0.5, num_train_timesteps, dtype=torch.float32) ** 2
-        elif beta_schedule == "linear":
-            betas = torch.linspace(beta_start, beta_end, num_train_timesteps, dtype=torch.float32)
-        else:
-            raise NotImplementedError(beta_schedule)
+        betas = _betas(beta_schedule, beta_start, beta_end, num_train_timesteps)
         self.config = dict(num_train_timesteps=num_train_timesteps, beta_start=beta_start, beta_end=beta_end,
                            beta_schedule=beta_schedule, solver_order=solver_order, prediction_type=prediction_type,
                            predict_x0=predict_x0, solver_type=solver_type, lower_order_final=lower_order_final,
@@ -174,12 +237,6 @@ class UniPCMultistepScheduler:
         self.sigmas = None
         self._reset()
 
-    @classmethod
-    def from_config(cls, config, **overrides):
-        c = dict(config) if not isinstance(config, cls) else dict(config.config)
-        c.update(overrides)
-        return cls(**c)
-
     def _reset(self):
         self.model_outputs = [None] * self.solver_order
         self.lower_order_nums = 0
@@ -190,18 +247,7 @@ class UniPCMultistepScheduler:
     def set_timesteps(self, num_inference_steps: int, device=None):
         import numpy as np
 
-        n_train = self.num_train_timesteps
-        sp = self.config["timestep_spacing"]
-        if sp == "linspace":
-            ts = np.linspace(0, n_train - 1, num_inference_steps + 1).round()[::-1][:-1].copy().astype(np.int64)
-        elif sp == "leading":
-            ratio = n_train // (num_inference_steps + 1)
-            ts = (np.arange(0, num_inference_steps + 1) * ratio).round()[::-1][:-1].copy().astype(np.int64)
-            ts += self.config["steps_offset"]
-        elif sp == "trailing":
-            ts = (np.arange(n_train, 0, -n_train / num_inference_steps).round() - 1).astype(np.int64)
-        else:
-            raise ValueError(sp)
+        ts = self._multistep_timesteps(num_inference_steps)
         ac = self.alphas_cumprod.numpy().astype(np.float64)
         sig = ((1 - ac) / ac) ** 0.5
         sigmas = np.interp(ts, np.arange(0, len(sig)), sig)
@@ -210,14 +256,6 @@ class UniPCMultistepScheduler:
         self.timesteps = torch.from_numpy(ts).to(device=device, dtype=torch.int64)
         self.num_inference_steps = len(ts)
         self._reset()
-
-    def scale_model_input(self, sample, timestep=None):
-        return sample
-
-    @staticmethod
-    def _alpha_sigma(sigma):
-        alpha_t = 1.0 / ((sigma ** 2 + 1.0) ** 0.5)
-        return alpha_t, sigma * alpha_t
 
     def _lambda(self, i):
         a, s = self._alpha_sigma(self.sigmas[i])
@@ -296,16 +334,8 @@ class UniPCMultistepScheduler:
         return torch.tensor(rows, dtype=torch.float32)
 
     # ---- diffusers protocol: one step on tensors ------------------------------------------------------------------
-    def _index_for(self, timestep):
-        t = int(torch.as_tensor(timestep).flatten()[0].item())
-        idx = (self.timesteps.cpu() == t).nonzero()
-        return int(idx[1 if len(idx) > 1 else 0]) if len(idx) else len(self.timesteps) - 1
-
     def convert_model_output(self, model_output, sample):
-        if self.prediction_type == "sample":
-            return model_output
-        a, s = self._alpha_sigma(self.sigmas[self._step_index])
-        return (sample - s * model_output) / a
+        return self._to_x0(model_output, sample, *self._alpha_sigma(self.sigmas[self._step_index]))
 
     def step(self, model_output: torch.Tensor, timestep, sample: torch.Tensor, return_dict: bool = False, **_):
         """One predictor-corrector step.  Arithmetic in fp32 whatever the input dtypes, the two samples (corrected
@@ -345,12 +375,6 @@ class UniPCMultistepScheduler:
         self._step_index += 1
         return (prev,) if not return_dict else {"prev_sample": prev}
 
-    def add_noise(self, original, noise, timesteps):
-        a = self.alphas_cumprod.to(original.device)[timesteps.long()].to(original.dtype)
-        while a.dim() < original.dim():
-            a = a[..., None]
-        return a.sqrt() * original + (1 - a).sqrt() * noise
-
 
 # ---------------------------------------------------------------------------------------------------------------------
 # Samplers that are one linear multistep recurrence with a noise term (ur_sde_update):
@@ -382,20 +406,7 @@ def _linear_step(row64, m, sample, m_prev, generator, variance_noise):
     return out.to(sample.dtype)
 
 
-def _betas(beta_schedule: str, beta_start: float, beta_end: float, n: int) -> torch.Tensor:
-    if beta_schedule == "scaled_linear":
-        return torch.linspace(beta_start ** 0.5, beta_end ** 0.5, n, dtype=torch.float32) ** 2
-    if beta_schedule == "linear":
-        return torch.linspace(beta_start, beta_end, n, dtype=torch.float32)
-    raise NotImplementedError(f"beta_schedule {beta_schedule!r}: scaled_linear and linear are implemented")
-
-
-def _config_of(config, cls):
-    c = dict(getattr(config, "config", config))
-    return {k: v for k, v in c.items() if not k.startswith("_")}
-
-
-class DDPMScheduler:
+class DDPMScheduler(_Scheduler):
     """DDPM ancestral sampling (Ho et al. 2020, eq. 7 and 11), restated from the published algorithm as diffusers 0.24's
     ``DDPMScheduler`` parameterises it: ``variance_type`` ``fixed_small`` (the posterior variance, clamped at 1e-20) /
     ``fixed_large`` (beta_t), no noise at t = 0, ``leading`` / ``linspace`` / ``trailing`` timestep spacing,
@@ -406,9 +417,6 @@ class DDPMScheduler:
 
     NOT implemented (``NotImplementedError``): ``clip_sample=True`` (so the default here is False, diffusers' is True),
     ``thresholding``, the learned variance types, ``v_prediction``, custom timestep lists."""
-
-    order = 1
-    init_noise_sigma = 1.0
 
     def __init__(self, num_train_timesteps: int = 1000, beta_start: float = 0.0001, beta_end: float = 0.02,
                  beta_schedule: str = "linear", variance_type: str = "fixed_small", clip_sample: bool = False,
@@ -433,12 +441,6 @@ class DDPMScheduler:
         self.num_inference_steps = None
 
     @classmethod
-    def from_config(cls, config, **overrides):
-        c = _config_of(config, cls)
-        c.update(overrides)
-        return cls(**c)
-
-    @classmethod
     def from_pretrained(cls, pretrained_model_name_or_path: str, subfolder: Optional[str] = None, **overrides):
         """Reads ``<path>/<subfolder>/scheduler_config.json`` (the diffusers layout)."""
         import json
@@ -453,7 +455,7 @@ class DDPMScheduler:
         n_train, sp = self.num_train_timesteps, self.config["timestep_spacing"]
         if num_inference_steps > n_train:
             raise ValueError("num_inference_steps > num_train_timesteps")
-        if sp == "linspace":
+        if sp == "linspace":  # n points: not the (n + 1)-point grid of the multistep solvers
             ts = np.linspace(0, n_train - 1, num_inference_steps).round()[::-1].copy().astype(np.int64)
         elif sp == "leading":
             ts = (np.arange(0, num_inference_steps) * (n_train // num_inference_steps)).round()[::-1].copy().astype(np.int64)
@@ -462,9 +464,6 @@ class DDPMScheduler:
             ts = (np.round(np.arange(n_train, 0, -n_train / num_inference_steps)) - 1).astype(np.int64)
         self.num_inference_steps = num_inference_steps
         self.timesteps = torch.from_numpy(ts).to(device)
-
-    def scale_model_input(self, sample, timestep=None):
-        return sample
 
     def _row64(self, t: int):
         ac = self.alphas_cumprod
@@ -488,22 +487,13 @@ class DDPMScheduler:
     def step(self, model_output: torch.Tensor, timestep, sample: torch.Tensor, generator=None,
              variance_noise: Optional[torch.Tensor] = None, return_dict: bool = False, **_):
         t = int(torch.as_tensor(timestep).flatten()[0].item())
-        m = model_output
-        if self.prediction_type == "epsilon":
-            cd = torch.float64 if sample.dtype == torch.float64 else torch.float32
-            a_t = float(self.alphas_cumprod[t])
-            m = (sample.to(cd) - (1 - a_t) ** 0.5 * model_output.to(cd)) / a_t ** 0.5
+        a_t = float(self.alphas_cumprod[t])
+        m = self._to_x0(model_output, sample, a_t ** 0.5, (1 - a_t) ** 0.5)
         prev = _linear_step(self._row64(t), m, sample, None, generator, variance_noise)
         return (prev,) if not return_dict else {"prev_sample": prev}
 
-    def add_noise(self, original, noise, timesteps):
-        a = self.alphas_cumprod.to(original.device)[timesteps.long()].to(original.dtype)
-        while a.dim() < original.dim():
-            a = a[..., None]
-        return a.sqrt() * original + (1 - a).sqrt() * noise
 
-
-class DPMSolverMultistepScheduler:
+class DPMSolverMultistepScheduler(_Scheduler):
     """DPM-Solver++ (Lu et al. 2022, arXiv 2211.01095: Algorithm 1 = first order, Algorithm 2 = 2M) and its SDE variant
     (Sec. 5 / eq. 18 of the same paper's v2), restated from the published algorithms as diffusers 0.24's
     ``DPMSolverMultistepScheduler`` parameterises them: data prediction, ``algorithm_type`` ``dpmsolver++`` /
@@ -524,8 +514,7 @@ class DPMSolverMultistepScheduler:
     ``solver_type="heun"``, ``euler_at_final``, ``thresholding``, ``lambda_min_clipped``, the learned ``variance_type``s,
     ``v_prediction``."""
 
-    init_noise_sigma = 1.0
-    order = 1
+    _config_drop = ("predict_x0", "disable_corrector")  # a UniPC config names these; they have no meaning here
 
     def __init__(self, num_train_timesteps: int = 1000, beta_start: float = 0.0001, beta_end: float = 0.02,
                  beta_schedule: str = "linear", solver_order: int = 2, prediction_type: str = "epsilon",
@@ -563,13 +552,10 @@ class DPMSolverMultistepScheduler:
 
     @classmethod
     def from_config(cls, config, **overrides):
-        c = _config_of(config, cls)
-        for k in ("predict_x0", "disable_corrector"):  # a UniPC config names these; they have no meaning here
-            c.pop(k, None)
-        if isinstance(config, UniPCMultistepScheduler) or "solver_type" in c and c["solver_type"] in ("bh1", "bh2"):
-            c.pop("solver_type", None)
-        c.update(overrides)
-        return cls(**c)
+        c = _config_of(config)
+        if c.get("solver_type") in ("bh1", "bh2"):  # UniPC's B(h) variant, not a DPM-Solver type
+            del c["solver_type"]
+        return super().from_config(c, **overrides)
 
     def _reset(self):
         self._m_prev = None
@@ -578,15 +564,7 @@ class DPMSolverMultistepScheduler:
     def set_timesteps(self, num_inference_steps: int, device=None):
         import numpy as np
 
-        n_train, sp = self.num_train_timesteps, self.config["timestep_spacing"]
-        if sp == "linspace":
-            ts = np.linspace(0, n_train - 1, num_inference_steps + 1).round()[::-1][:-1].copy().astype(np.int64)
-        elif sp == "leading":
-            ratio = n_train // (num_inference_steps + 1)
-            ts = (np.arange(0, num_inference_steps + 1) * ratio).round()[::-1][:-1].copy().astype(np.int64)
-            ts += self.config["steps_offset"]
-        else:
-            ts = (np.arange(n_train, 0, -n_train / num_inference_steps).round() - 1).astype(np.int64)
+        ts = self._multistep_timesteps(num_inference_steps)
         ac = self.alphas_cumprod.numpy().astype(np.float64)
         sig = ((1 - ac) / ac) ** 0.5
         if self.config["use_karras_sigmas"]:
@@ -602,14 +580,6 @@ class DPMSolverMultistepScheduler:
         self.timesteps = torch.from_numpy(ts).to(device=device, dtype=torch.int64)
         self.num_inference_steps = len(ts)
         self._reset()
-
-    def scale_model_input(self, sample, timestep=None):
-        return sample
-
-    @staticmethod
-    def _alpha_sigma(sigma):
-        alpha_t = 1.0 / ((sigma ** 2 + 1.0) ** 0.5)
-        return alpha_t, sigma * alpha_t
 
     def _orders(self):
         """The order of the update at every step index (first-order warm-up, lower_order_final)."""
@@ -649,11 +619,6 @@ class DPMSolverMultistepScheduler:
         """[n, 4] fp32 rows (p0, p1, p2, pn) for ``ur_sde_update``; pn = 0 throughout for ``dpmsolver++``."""
         return torch.tensor(self._rows64(), dtype=torch.float32).reshape(-1, 4)
 
-    def _index_for(self, timestep):
-        t = int(torch.as_tensor(timestep).flatten()[0].item())
-        idx = (self.timesteps.cpu() == t).nonzero()
-        return int(idx[1 if len(idx) > 1 else 0]) if len(idx) else len(self.timesteps) - 1
-
     def step(self, model_output: torch.Tensor, timestep, sample: torch.Tensor, generator=None,
              variance_noise: Optional[torch.Tensor] = None, return_dict: bool = False, **_):
         """One multistep update: the fp32 row of ``coefficient_table`` in the kernel's order, one rounding to
@@ -664,20 +629,67 @@ class DPMSolverMultistepScheduler:
             self._step_index = self._index_for(timestep)
         i = min(self._step_index, self.num_inference_steps - 1)
         cd = torch.float64 if sample.dtype == torch.float64 else torch.float32
-        m = model_output.to(cd)
-        if self.prediction_type == "epsilon":
-            a, s = self._alpha_sigma(float(self.sigmas[i]))
-            m = (sample.to(cd) - s * m) / a
+        m = self._to_x0(model_output.to(cd), sample, *self._alpha_sigma(float(self.sigmas[i])))
         prev = _linear_step(self._rows64()[i], m, sample, self._m_prev, generator, variance_noise)
         self._m_prev = m
         self._step_index += 1
         return (prev,) if not return_dict else {"prev_sample": prev}
 
-    def add_noise(self, original, noise, timesteps):
-        a = self.alphas_cumprod.to(original.device)[timesteps.long()].to(original.dtype)
-        while a.dim() < original.dim():
-            a = a[..., None]
-        return a.sqrt() * original + (1 - a).sqrt() * noise
+
+# ---------------------------------------------------------------------------------------------------------------------
+# What the on-device sampling loop needs to know about a scheduler, in one place.
+# ---------------------------------------------------------------------------------------------------------------------
+@dataclass(frozen=True)
+class DevicePlan:
+    """A scheduler's loop as the update kernels run it.  ``kind``: ``"ddim"`` (``ur_ddim_update``, [n, 4] square-root rows),
+    ``"unipc"`` (``ur_unipc_update``, [n, 8]) or ``"sde-<ClassName>"`` (``ur_sde_update``, [n, 4] rows p0 p1 p2 pn); ``coef``:
+    that table, fp32 on the CPU; ``tvals``: the timesteps as fp32 [n]; ``noisy``: some row has a noise weight.  Plans are
+    shared between calls: read-only."""
+    kind: str
+    coef: torch.Tensor
+    tvals: torch.Tensor
+    noisy: bool
+
+    def step_kwargs(self, eta: float, noise) -> dict:
+        """The keywords of the scheduler's own ``step`` in a step-by-step loop (the reference's
+        ``prepare_extra_step_kwargs``): ``eta`` for DDIM only, the step's noise for the three classes that take it."""
+        kw = {}
+        if self.kind == "sde-DDIMScheduler":
+            kw["eta"] = eta
+        if noise is not None and self.kind != "unipc":
+            kw["variance_noise"] = noise
+        return kw
+
+
+_PLANS: dict = {}  # schedule -> plan: the eight equal schedulers of a pipeline share one table, and so do its calls
+
+
+def device_plan(sched, eta: float = 0.0) -> Optional[DevicePlan]:
+    """The plan of ``sched`` (after ``set_timesteps``) with DDIM's ``eta``, or None for an object that is not exactly one of
+    this module's four classes (subclasses and foreign protocol objects take the step-by-step loop).  THE place that maps a
+    scheduler to its kernel, table and state.  A UniPC table costs milliseconds, so plans are kept per schedule (class,
+    config, eta, timesteps, alphas_cumprod / sigmas by value)."""
+    cls = type(sched)
+    if cls not in (DDIMScheduler, UniPCMultistepScheduler, DDPMScheduler, DPMSolverMultistepScheduler):
+        return None
+    eta = float(eta) if cls is DDIMScheduler else 0.0
+    raw = lambda t: None if t is None else t.detach().cpu().numpy().tobytes()
+    key = (cls, eta, sched.num_inference_steps, tuple(sorted(sched.config.items())), raw(sched.timesteps),
+           raw(sched.alphas_cumprod), raw(getattr(sched, "sigmas", None)), raw(getattr(sched, "final_alpha_cumprod", None)))
+    plan = _PLANS.get(key)
+    if plan is None:
+        if cls is DDIMScheduler and eta == 0.0:
+            kind, coef = "ddim", sched._sqrt_rows()
+        elif cls is UniPCMultistepScheduler:
+            kind, coef = "unipc", sched.coefficient_table()
+        else:
+            kind, coef = "sde-" + cls.__name__, (sched.coefficient_table(eta) if cls is DDIMScheduler else sched.coefficient_table())
+        noisy = kind.startswith("sde-") and bool((coef[:, 3] != 0).any())
+        plan = DevicePlan(kind, coef, sched.timesteps.detach().cpu().to(torch.float32), noisy)
+        if len(_PLANS) >= 64:
+            _PLANS.clear()
+        _PLANS[key] = plan
+    return plan
 
 
 def _refused(name: str, why: str):
