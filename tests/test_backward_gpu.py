@@ -640,3 +640,92 @@ def test_layernorm_skip_node(dev, dtype):
     yr = F.layer_norm(xr, (C,), g_.cpu(), b_.cpu(), 1e-5) @ w.float().cpu().t() + xr
     yr.backward(up.float().cpu())
     assert rel_l2(dx1, xr.grad) < TOL[dtype]
+
+
+def _ints(shape, lim, seed):
+    return torch.randint(-lim, lim + 1, shape, generator=torch.Generator().manual_seed(seed)).float()
+
+
+@pytest.mark.parametrize("co,ci,cpad", [(64, 4, 64), (64, 72, None)])  # conv_in's (padded to CIN_PAD); Ci a multiple of 8, not of 64
+def test_single_and_grouped_conv_pack_nodes_agree(dev, co, ci, cpad):
+    """PackConvWeight (one weight, the path outside a stage) and PackConvWeights (all of a network's, behind the barrier) on the
+    same fp32 weight and the same packed upstream gradient: the same packed weight, the same fp32 gradient, the same sums of
+    squares for the clipping norm, bit for bit.  Integer data with |v| <= 8: every sum (<= 64 * 72 * 9 * 64 < 2^24) is exact,
+    so the expected values are known too."""
+    from uni_renderer_amd import autograd_ops as A, backward as bw
+    from uni_renderer_amd.controlnet import CIN_PAD
+    assert cpad in (None, CIN_PAD)
+    cp = ci if cpad is None else cpad
+    w0 = _ints((co, ci, 3, 3), 8, co + ci).to(dev)
+    up = _ints((co, 9 * cp), 8, ci).to(torch.bfloat16).to(dev)
+
+    def run(grouped):
+        w = w0.clone().requires_grad_()
+        bw.grad_squares.begin()
+        if grouped:
+            (wp,) = A.PackConvWeights.apply(torch.bfloat16, (cpad,), w)
+        else:
+            wp = A.PackConvWeight.apply(w, torch.bfloat16, cpad)
+        wp.backward(up)
+        gs = bw.grad_squares
+        assert gs.count == {id(w): 1} and len(gs.parts) == 1
+        return wp.detach(), w.grad, gs.parts[0]
+
+    wp1, g1, sq1 = run(False)
+    wpn, gn, sqn = run(True)
+    bw.grad_squares.clear()
+    assert torch.equal(wp1, wpn) and torch.equal(g1, gn) and torch.equal(sq1, sqn)
+    assert (wpn.data_ptr(), tuple(wpn.shape)) not in bw.weight_rot  # the grouped node released the rotated form it derived
+    want = torch.zeros(co, 3, 3, cp, device=dev)
+    want[..., :ci] = w0.permute(0, 2, 3, 1)
+    assert torch.equal(wp1.float(), want.reshape(co, 9 * cp))
+    gwant = up.float().view(co, 3, 3, cp)[..., :ci].permute(0, 3, 1, 2)
+    assert g1.dtype == torch.float32 and torch.equal(g1, gwant)
+    assert float(sq1.sum()) == float((gwant.double() ** 2).sum())
+
+
+def test_staged_and_unstaged_layers_give_the_same_gradients(dev):
+    """A Linear + Conv3x3 pair inside a ``param_stage.Stage`` (weights cast / packed up front, all four gradients deferred behind
+    the barrier nodes and computed by grouped launches) and outside one (plain cast, a PackConvWeight node, every gradient
+    computed where it arises): the fp32 ``.grad`` of both weights and both biases bit for bit.  This is the fallback the
+    recompute of a gradient-checkpointed resnet runs on.  M = 64 rows, K = N = 64, a 4x4 map at 64 channels: ``wgrad_ok`` takes
+    both, so both sides go through the weight-gradient kernel.  Integers: |x| <= 4, |w|, |b|, |dy| <= 2, so the largest sum --
+    the Linear weight gradient, 64 rows of |dy . w| <= 9 * 64 * 4 times |x| <= 4 -- stays below 2^24 and no order of summation
+    rounds."""
+    import torch.nn as nn
+
+    from uni_renderer_amd import autograd_ops as A, backward as bw, param_stage as PS
+
+    class Pair(nn.Module):
+        def __init__(self):
+            super().__init__()
+            self.lin, self.conv = nn.Linear(64, 64), nn.Conv2d(64, 64, 3, padding=1)
+
+    net, dt = Pair().to(dev), torch.bfloat16
+    with torch.no_grad():
+        for i, p in enumerate(net.parameters()):
+            p.copy_(_ints(tuple(p.shape), 2, 11 + i))
+    x = _ints((64, 64), 4, 1).to(dt).to(dev)
+    up = _ints((4, 4, 4, 64), 2, 2).to(dt).to(dev)
+    assert bw.wgrad_ok(up.view(64, 64), x) and bw.wgrad_ok(up.view(64, 64), up, (4, 4))
+
+    def run(staged):
+        for p in net.parameters():
+            p.grad = None
+        bw.wgrad_queue.reset()
+        with PS.Stage(net, dt) if staged else torch.enable_grad() as st:
+            if staged:
+                assert set(st.weights) == {id(net.lin.weight)} and set(st.packed) == {(id(net.conv.weight), None)}
+                assert set(st.vectors) == {id(net.lin.bias), id(net.conv.bias)}
+            h = A.linear(x, PS.w2(net.lin, dt), net.lin.bias)
+            y = A.conv3x3(h.view(4, 4, 4, 64), A.pack_conv_weight(net.conv.weight, dt), net.conv.bias)
+        assert h.grad_fn.defer == staged and y.grad_fn.defer == staged
+        y.backward(up)
+        assert not bw.wgrad_queue.items                    # the barriers flushed what was deferred
+        return y.detach(), [p.grad for p in net.parameters()]
+
+    y1, g1 = run(True)
+    y0, g0 = run(False)
+    assert torch.equal(y1, y0)
+    for a, b in zip(g1, g0):
+        assert a.dtype == torch.float32 and torch.equal(a, b) and float(a.abs().max()) > 0

@@ -2,7 +2,9 @@
 import pytest
 import torch
 
+from uni_renderer_amd import param_stage as PS
 from uni_renderer_amd import train_step as TS
+from uni_renderer_amd.controlnet import CIN_PAD
 
 
 class _Net(torch.nn.Module):
@@ -23,19 +25,87 @@ def test_parameter_list_is_cached_per_network_tuple():
     assert TS._parameters(other) is not ps and TS._parameters(other)[0] is other[0].lin.weight
 
 
+def _staged(stage):
+    return (stage.weights, stage.merged, stage.vectors, stage.packed)
+
+
 def test_batched_casts_cover_linear_and_1x1_weights_and_fail_loudly_on_cpu():
     net = _Net()
-    with torch.no_grad():                                  # inference: nothing is cast up front
-        with TS._batched_casts(net, torch.bfloat16):
-            assert TS._cast == {}
+    with torch.no_grad():                                  # inference: nothing is staged up front
+        with PS.Stage(net, torch.bfloat16) as st:
+            assert PS.active is st and not any(_staged(st))
+    assert PS.active is None
     with pytest.raises(RuntimeError):                      # training on CPU tensors: no CPU fallback
-        with TS._batched_casts(net, torch.bfloat16):
+        with PS.Stage(net, torch.bfloat16):
             pass
-    ws = TS._castable[id(net)][1]
+    ws = PS.plan(net).matrices
     assert {id(w) for w in ws} == {id(net.lin.weight), id(net.c1.weight)}  # Linear + 1x1 conv; not the 3x3, not the norm
-    assert TS._cast == {}
-    w = TS._wc(net.lin.weight, torch.bfloat16)             # outside a batched cast: the plain differentiable cast
+    assert PS.active is None                               # after leaving, by the exception too: nothing is staged
+    w = PS.wc(net.lin.weight, torch.bfloat16)              # outside a stage: the plain differentiable cast
     assert w.dtype == torch.bfloat16 and w.requires_grad
+
+
+def test_a_dropped_network_takes_its_stage_plan_along():
+    import gc
+
+    net = _Net()
+    assert PS.plan(net) is PS.plan(net) and net in PS._plans
+    del net
+    gc.collect()
+    assert len(PS._plans) == 0
+
+
+def test_a_stage_left_by_an_exception_leaves_nothing_to_the_next_one():
+    a, b = _Net(), _Net()
+    with torch.no_grad():
+        with pytest.raises(KeyError):
+            with PS.Stage(a, torch.bfloat16) as st:
+                st.weights[id(a.lin.weight)] = a.lin.weight.to(torch.bfloat16)   # as if staged
+                st.vectors[id(a.lin.bias)] = a.lin.bias
+                assert PS.wc(a.lin.weight, torch.bfloat16) is st.weights[id(a.lin.weight)]
+                raise KeyError("in the body")
+        assert PS.active is None
+        with PS.Stage(b, torch.bfloat16) as st2:
+            assert PS.active is st2 and not any(_staged(st2))
+            assert PS.wc(a.lin.weight, torch.bfloat16) is not st.weights[id(a.lin.weight)]
+        with pytest.raises(RuntimeError):                  # the networks run one after the other: no stage inside a stage
+            with PS.Stage(a, torch.bfloat16):
+                with PS.Stage(b, torch.bfloat16):
+                    pass
+    assert PS.active is None
+
+
+def test_stage_plan_order_keeps_concatenated_operands_adjacent_and_leaves_the_narrow_convs_out():
+    """The packed copies lie in plan order and ``cat_adjacent`` relies on it: all time_emb_proj, then the to_k / to_v pairs of
+    the cross-attentions, then the rest in module order.  The seven narrow convs of a ControlNet conditioning embedding are
+    neither packed nor put behind the bias barrier (CondConv3x3 reads the parameters themselves); its conv_out is an ordinary
+    3x3 conv."""
+    from uni_renderer_amd.layers import BasicTransformerBlock, ControlNetConditioningEmbedding, ResnetBlock2D
+
+    class Toy(torch.nn.Module):
+        def __init__(self):
+            super().__init__()
+            self.conv_in = torch.nn.Conv2d(4, 32, 3, padding=1)
+            self.r0 = ResnetBlock2D(32, 32, 128, groups=8)
+            self.tb = BasicTransformerBlock(32, 2, 16, 64)
+            self.r1 = ResnetBlock2D(64, 32, 128, groups=8)           # with a 1x1 shortcut
+            self.controlnet_cond_embedding = ControlNetConditioningEmbedding(32, 3, (16, 32))
+
+    net = Toy()
+    p = PS.plan(net)
+    tb, emb = net.tb, net.controlnet_cond_embedding
+    rest = [tb.attn1.to_q.weight, tb.attn1.to_k.weight, tb.attn1.to_v.weight, tb.attn1.to_out[0].weight, tb.attn2.to_q.weight,
+            tb.attn2.to_out[0].weight, tb.ff.net[0].proj.weight, tb.ff.net[2].weight, net.r1.conv_shortcut.weight]
+    want = [net.r0.time_emb_proj.weight, net.r1.time_emb_proj.weight, tb.attn2.to_k.weight, tb.attn2.to_v.weight] + rest
+    assert [id(w) for w in p.matrices] == [id(w) for w in want]
+    narrow = [emb.conv_in] + list(emb.blocks)
+    assert len(narrow) == 3 and all(m.kernel_size == (3, 3) for m in narrow)
+    vec, c3 = {id(v) for v in p.vectors}, {id(w): cp for w, cp in p.convs}
+    assert not any(id(m.bias) in vec or id(m.weight) in c3 for m in narrow)
+    assert id(emb.conv_out.bias) in vec and c3[id(emb.conv_out.weight)] is None
+    assert c3[id(net.conv_in.weight)] == CIN_PAD and id(net.r0.norm1.weight) in vec and id(tb.norm3.bias) in vec
+    assert [id(w) for w, _ in p.convs] == [id(m.weight) for m in (net.conv_in, net.r0.conv1, net.r0.conv2, net.r1.conv1,
+                                                                   net.r1.conv2, emb.conv_out)]
 
 
 def test_derived_weight_cache_never_serves_a_dead_buffer():

@@ -195,6 +195,11 @@ network call, the plain decode, and peak allocated memory of each).
 `csrc/sampler.hip`: device assembly function by function, the latents of every sampler / guidance / latent dtype / MultiDiffusion
 call of the tree before against the tree after, fused and step by step, `bench.py`'s `loop_parity` numbers, the alternating speed
 lines of the 50-step loops and the folded UniPC call, line counts).
+`param_stage_ab.txt` (the training path's staged parameters behind one `param_stage.Stage` per network forward, the barrier nodes of
+`autograd_ops.py` on shared helpers, `train_step.py` split from `autograd_net.py`: loss and SHA-256 of every parameter gradient of
+the parent's Python against the new tree's over the same library -- tiny and SD size, both objectives, with and without gradient
+buckets and checkpointing, LoRA, ControlNet, graph replays --, kernel launches of an eager step, `wgrad_queue.trace`, the
+alternating `tools/train_bench.py` lines, line counts).
 
 | file | what |
 |---|---|

@@ -34,7 +34,7 @@ KNOWN = {
     "heads_multi": "split / merge heads of several tensors in one launch (backward.py)",
     "flash_backward": "flash attention backward instead of the materialised-P path (backward.py)",
     "forward_lse": "the forward attention hands its row log-sum-exp to the backward (backward.py)",
-    "batch_casts": "fp32 -> bf16 parameter casts of a network in one launch group (train_step.py)",
+    "batch_casts": "fp32 -> bf16 parameter casts of a network in one launch group (param_stage.py)",
     "gn_resident": "one-launch GroupNorm keeps small strips in registers: one memory round trip (ops.py, csrc/norm.hip)",
     "head_major_qk": "the chain kernels write q / k of the d = 40 attention as [sample][head][token][40] images (fused.py)",
     # ---- on-switches of measured-slower paths ----

@@ -1,45 +1,69 @@
 """torch.autograd Functions over the HIP ops: forward = the forward kernels of ``ops``, backward = the building blocks
-of ``backward`` (device op 11).  They let the training step (train_step.py; reference
+of ``backward`` (device op 11).  They let the networks of the training step (autograd_net.py; reference
 train/train.py:1258-1427) be written as an ordinary forward pass -- autograd only does the graph bookkeeping (skip
-connections, concatenations, dtype casts of the fp32 master parameters); every gradient is computed by this package's
-kernels.  All tensors are NHWC / token matrices in the compute dtype (bf16 or fp16); biases and norm parameters fp32.
+connections, concatenations); every gradient is computed by this package's kernels.  All tensors are NHWC / token matrices
+in the compute dtype (bf16 or fp16); biases and norm parameters fp32.
+
+CastParams, LoraMerge, PackConvWeights and ParamBarrier are barrier nodes over the parameters of a whole network
+(``param_stage.Stage`` issues them): their backward runs when the LAST gradient of their outputs has arrived, and reads
+"flush the deferred weight-gradient queue, release the derived forms, deliver the fp32 gradients".
 """
 from __future__ import annotations
+
+import weakref
 
 import torch
 from torch.autograd import Function
 
-from . import _lib, backward as bw, ops
+from . import _lib, backward as bw, ops, param_stage as PS
 from ._lib import check
 from .ops import DT, _stream
 
 
 # Deferred weight gradients (backward.WgradQueue): a Linear may hand autograd UNINITIALISED dw / db tensors only if their first
-# reader flushes the queue first.  That is the case for weights that are (views of) a CastParams output and biases that are a
-# ParamBarrier output; both register here, by storage / data pointer, with a weak reference that dies with the autograd graph.
-_deferred_w: dict = {}   # storage data_ptr of a CastParams buffer -> weakref(buffer)
-_deferred_b: dict = {}   # data_ptr of a ParamBarrier output      -> weakref(output)
-deferred_bias: dict = {}  # id(fp32 bias parameter) -> its ParamBarrier output for the current network forward (train_step)
+# reader flushes the queue first.  That is the case for weights that are (views of) a barrier node's output buffer and biases that
+# are a ParamBarrier output; both register here, by storage / data pointer, with a weak reference that dies with the autograd graph.
+_deferred_w: dict = {}   # storage data_ptr of a CastParams / LoraMerge / PackConvWeights buffer -> weakref(buffer)
+_deferred_b: dict = {}   # data_ptr of a ParamBarrier output -> weakref(output)
 
 
-def _alive(table: dict, ptr: int) -> bool:
-    ref = table.get(ptr)
-    if ref is None:
-        return False
-    t = ref()
-    if t is None:
-        del table[ptr]
-        return False
-    return True
+def _defer_views_of(flat):
+    """the weight gradients of (views of) the buffer ``flat`` may be deferred: its node flushes the queue before it reads them"""
+    _deferred_w[flat.untyped_storage().data_ptr()] = weakref.ref(flat)
+
+
+def _derive_wt(outs, flat) -> list:
+    """W^T of the matrices ``outs`` (views of ``flat``) for the dx GEMMs of the backward, 32 per launch; returns the keys under
+    which ``bw.weight_t`` holds them while ``flat`` is alive (the node's backward releases them)."""
+    keys = []
+    bw.weight_t.sweep()  # entries of a forward that was never backpropagated, whose buffer is gone
+    if bw.BATCH_WT and bw.WGRAD:
+        w2 = [o.reshape(o.shape[0], -1) for o in outs if o.dim() >= 2]
+        w2 = [o for o in w2 if o.shape[0] % 8 == 0 and o.shape[1] % 8 == 0 and o.numel()]
+        for o, t in zip(w2, bw.transpose2d_many(w2) if w2 else []):
+            keys.append((o.data_ptr(), tuple(o.shape)))
+            bw.weight_t.put(keys[-1], flat, t)
+    return keys
+
+
+def _release(cache, keys):
+    for key in keys:
+        cache.pop(key, None)
+
+
+def _is_barrier(t) -> bool:
+    """``t`` is the very output OBJECT of a live ParamBarrier (not merely a tensor at the parameter's address)"""
+    ref = _deferred_b.get(t.data_ptr())
+    return ref is not None and ref() is t
 
 
 def _can_defer(w, b) -> bool:
-    if not bw.WGRAD_DEFER or not bw.WGRAD or not _alive(_deferred_w, w.untyped_storage().data_ptr()):
+    ptr = w.untyped_storage().data_ptr()
+    ref = _deferred_w.get(ptr) if (bw.WGRAD_DEFER and bw.WGRAD) else None
+    if ref is not None and ref() is None:
+        del _deferred_w[ptr]  # the buffer that was registered at this address is gone
         return False
-    if b is None:
-        return True
-    ref = _deferred_b.get(b.data_ptr())
-    return ref is not None and ref() is b   # the barrier's output OBJECT, not merely a tensor at the parameter's address
+    return ref is not None and (b is None or _is_barrier(b))
 
 
 class Linear(Function):
@@ -71,7 +95,6 @@ class ParamBarrier(Function):
 
     @staticmethod
     def forward(ctx, *params):
-        import weakref
         ctx.set_materialize_grads(False)
         ctx.pids = [id(p) for p in params]
         outs = tuple(torch.empty(0, dtype=p.dtype, device=p.device).set_(p.untyped_storage(), p.storage_offset(), p.shape, p.stride())
@@ -166,27 +189,17 @@ class Up2x(Function):
         return bw.resample2x(dy.contiguous(), 1)
 
 
-def _is_barrier(t) -> bool:
-    """``t`` is the very output object of a live ParamBarrier (its gradient may be handed out uninitialised)."""
-    ref = _deferred_b.get(t.data_ptr())
-    return ref is not None and ref() is t
-
-
-def _norm_params(gamma, beta):
-    """the ParamBarrier outputs of a norm layer's parameters inside a batched-cast context (train_step), else themselves"""
-    if deferred_bias:
-        return deferred_bias.get(id(gamma), gamma), deferred_bias.get(id(beta), beta)
-    return gamma, beta
+def _staged(p):
+    """the ParamBarrier output of the fp32 vector ``p`` (a bias, gamma, beta) inside a network's stage, else ``p`` itself"""
+    return PS.active.vectors.get(id(p), p) if (PS.active is not None and p is not None) else p
 
 
 def group_norm(x, gamma, beta, eps, groups, silu):
-    gamma, beta = _norm_params(gamma, beta)
-    return GroupNorm.apply(x, gamma, beta, eps, groups, silu)
+    return GroupNorm.apply(x, _staged(gamma), _staged(beta), eps, groups, silu)
 
 
 def layer_norm_skip(x, gamma, beta, eps):
-    gamma, beta = _norm_params(gamma, beta)
-    return LayerNormSkip.apply(x, gamma, beta, eps)
+    return LayerNormSkip.apply(x, _staged(gamma), _staged(beta), eps)
 
 
 class GroupNorm(Function):
@@ -342,15 +355,11 @@ class Add(Function):
 
 
 def linear(x, w, b=None, res=None, rowadd=None, rows_per_b=0):
-    if b is not None and deferred_bias:
-        b = deferred_bias.get(id(b), b)
-    return Linear.apply(x, w, b, res, rowadd, rows_per_b)
+    return Linear.apply(x, w, _staged(b), res, rowadd, rows_per_b)
 
 
 def conv3x3(x, wp, b=None, res=None, rowadd=None, stride=1):
-    if b is not None and deferred_bias:
-        b = deferred_bias.get(id(b), b)
-    return Conv3x3.apply(x, wp, b, res, rowadd, stride)
+    return Conv3x3.apply(x, wp, _staged(b), res, rowadd, stride)
 
 
 class CatAdjacent(Function):
@@ -386,112 +395,90 @@ def cat_adjacent(ts):
     return CatAdjacent.apply(*ts)
 
 
+def _pack_conv(weight, dtype, cin_pad):
+    """fp32 [Co, Ci, 3, 3] -> compute-dtype [Co][(ky, kx, ci_pad)] (ur_pack_conv_weight); returns it with (Co, Ci, ci_pad)"""
+    co, ci = weight.shape[:2]
+    cp = ci if cin_pad is None else cin_pad
+    out = torch.empty(co, 9 * cp, dtype=dtype, device=weight.device)
+    check(_lib.load().ur_pack_conv_weight(weight.detach().contiguous().data_ptr(), out.data_ptr(), co, ci, cp, DT[dtype], _stream()),
+          "ur_pack_conv_weight")
+    return out, (co, ci, cp)
+
+
+def _unpack_conv_grad(dwp, geom, pid):
+    """the packed gradient ``dwp`` as the fp32 [Co, Ci, 3, 3] gradient of parameter ``pid`` (ur_unpack_conv_weight_grad), written
+    into the parameter's slice of its communication bucket if it has one (bw.GradSink), its sum of squares to bw.GradSquares"""
+    lib = _lib.load()
+    co, ci, cp = geom
+    if dwp.stride(-1) != 1:
+        dwp = dwp.contiguous()
+    g = bw.grad_sink.take(pid)
+    if g is None or tuple(g.shape) != (co, ci, 3, 3):
+        g = torch.empty(co, ci, 3, 3, dtype=torch.float32, device=dwp.device)
+    if bw.FUSED_GRADNORM:
+        part = torch.empty(int(lib.ur_unpack_conv_weight_grad_blocks(co, ci)), dtype=torch.float32, device=dwp.device)
+        check(lib.ur_unpack_conv_weight_grad_sumsq(dwp.data_ptr(), dwp.stride(0), g.data_ptr(), co, ci, cp, part.data_ptr(),
+                                                   DT[dwp.dtype], _stream()), "ur_unpack_conv_weight_grad_sumsq")
+        bw.grad_squares.add(part, [pid])
+    else:
+        check(lib.ur_unpack_conv_weight_grad(dwp.data_ptr(), dwp.stride(0), g.data_ptr(), co, ci, cp, DT[dwp.dtype], _stream()),
+              "ur_unpack_conv_weight_grad")
+    return g
+
+
 class PackConvWeight(Function):
-    """fp32 master [Co, Ci, 3, 3] -> compute-dtype [Co][(ky, kx, ci_pad)] (ur_pack_conv_weight) and the packed weight
-    gradient back to an fp32 [Co, Ci, 3, 3] gradient (ur_unpack_conv_weight_grad): one kernel each way."""
+    """One 3x3 conv weight outside a stage: packed in the forward, its gradient unpacked in the backward, one kernel each way.
+    Nothing is deferred or derived up front: Conv3x3.backward computes this weight's gradient and rotated form itself."""
 
     @staticmethod
     def forward(ctx, weight, dtype, cin_pad):
-        lib = _lib.load()
-        co, ci = weight.shape[:2]
-        cp = ci if cin_pad is None else cin_pad
-        ctx.geom = (co, ci, cp)
         ctx.pid = id(weight)
-        w = weight.detach().contiguous()
-        out = torch.empty(co, 9 * cp, dtype=dtype, device=weight.device)
-        check(lib.ur_pack_conv_weight(w.data_ptr(), out.data_ptr(), co, ci, cp, DT[dtype], _stream()), "ur_pack_conv_weight")
+        out, ctx.geom = _pack_conv(weight, dtype, cin_pad)
         return out
 
     @staticmethod
     def backward(ctx, dwp):
-        lib = _lib.load()
-        co, ci, cp = ctx.geom
-        if dwp.stride(-1) != 1:
-            dwp = dwp.contiguous()
-        g = bw.grad_sink.take(ctx.pid)  # the parameter's slice of its communication bucket, or None
-        if g is None or tuple(g.shape) != (co, ci, 3, 3):
-            g = torch.empty(co, ci, 3, 3, dtype=torch.float32, device=dwp.device)
-        if bw.FUSED_GRADNORM:
-            part = torch.empty(int(lib.ur_unpack_conv_weight_grad_blocks(co, ci)), dtype=torch.float32, device=dwp.device)
-            check(lib.ur_unpack_conv_weight_grad_sumsq(dwp.data_ptr(), dwp.stride(0), g.data_ptr(), co, ci, cp, part.data_ptr(),
-                                                       DT[dwp.dtype], _stream()), "ur_unpack_conv_weight_grad_sumsq")
-            bw.grad_squares.add(part, [ctx.pid])
-        else:
-            check(lib.ur_unpack_conv_weight_grad(dwp.data_ptr(), dwp.stride(0), g.data_ptr(), co, ci, cp, DT[dwp.dtype], _stream()),
-                  "ur_unpack_conv_weight_grad")
         bw.wgrad_stats["matrices"] += 1
-        return g, None, None
+        return _unpack_conv_grad(dwp, ctx.geom, ctx.pid), None, None
 
 
 class PackConvWeights(Function):
-    """PackConvWeight for ALL 3x3 conv weights of a network as one autograd node: the packed copies are made up front, and the
-    backward runs when the last packed gradient has arrived -- it flushes the deferred weight-gradient queue first
-    (backward.WgradQueue: Conv3x3.backward hands out uninitialised dw for these weights), then unpacks every gradient."""
+    """PackConvWeight for ALL 3x3 conv weights of a network as one barrier node: the packed copies are made up front, and
+    Conv3x3.backward hands out uninitialised dw for these weights (backward.WgradQueue)."""
 
     @staticmethod
     def forward(ctx, dtype, cin_pads, *weights):
-        import weakref
-        lib = _lib.load()
         ctx.set_materialize_grads(False)
-        ctx.geoms, ctx.pids, outs = [], [id(w) for w in weights], []
-        for w_, cpad in zip(weights, cin_pads):
-            co, ci = w_.shape[:2]
-            cp = ci if cpad is None else cpad
-            ctx.geoms.append((co, ci, cp))
-            out = torch.empty(co, 9 * cp, dtype=dtype, device=w_.device)
-            check(lib.ur_pack_conv_weight(w_.detach().contiguous().data_ptr(), out.data_ptr(), co, ci, cp, DT[dtype], _stream()),
-                  "ur_pack_conv_weight")
-            _deferred_w[out.untyped_storage().data_ptr()] = weakref.ref(out)
-            outs.append(out)
-        # the dgrad form of every weight (taps rotated, channels transposed), 32 per launch (bw.weight_rot; dropped in the backward)
+        ctx.pids = [id(w) for w in weights]
+        packs = [_pack_conv(w_, dtype, cpad) for w_, cpad in zip(weights, cin_pads)]
+        outs, ctx.geoms = tuple(p[0] for p in packs), [p[1] for p in packs]
+        for out in outs:
+            _defer_views_of(out)
+        # the dgrad form of every weight (taps rotated, channels transposed), 32 per launch (bw.weight_rot)
         ctx.rot_keys = []
         bw.weight_rot.sweep()  # entries of a forward that was never backpropagated, whose packed weights are gone
         if bw.BATCH_WT:
             elig = [(o, g[2]) for o, g in zip(outs, ctx.geoms) if g[0] % 64 == 0 and g[2] % 8 == 0]
             for (o, _), r in zip(elig, bw.rot_weights_many(elig) if elig else []):
-                key = (o.data_ptr(), tuple(o.shape))
-                bw.weight_rot.put(key, o, r)  # valid while the packed weight `o` is alive
-                ctx.rot_keys.append(key)
-        return tuple(outs)
+                ctx.rot_keys.append((o.data_ptr(), tuple(o.shape)))
+                bw.weight_rot.put(ctx.rot_keys[-1], o, r)  # valid while the packed weight `o` is alive
+        return outs
 
     @staticmethod
     def backward(ctx, *grads):
-        lib = _lib.load()
         bw.wgrad_queue.flush()
-        for key in ctx.rot_keys:
-            bw.weight_rot.pop(key, None)
-        res = []
-        for dwp, (co, ci, cp), pid in zip(grads, ctx.geoms, ctx.pids):
-            if dwp is None:
-                res.append(None)
-                continue
-            if dwp.stride(-1) != 1:
-                dwp = dwp.contiguous()
-            g = bw.grad_sink.take(pid)  # the parameter's slice of its communication bucket, or None
-            if g is None or tuple(g.shape) != (co, ci, 3, 3):
-                g = torch.empty(co, ci, 3, 3, dtype=torch.float32, device=dwp.device)
-            if bw.FUSED_GRADNORM:
-                part = torch.empty(int(lib.ur_unpack_conv_weight_grad_blocks(co, ci)), dtype=torch.float32, device=dwp.device)
-                check(lib.ur_unpack_conv_weight_grad_sumsq(dwp.data_ptr(), dwp.stride(0), g.data_ptr(), co, ci, cp, part.data_ptr(),
-                                                           DT[dwp.dtype], _stream()), "ur_unpack_conv_weight_grad_sumsq")
-                bw.grad_squares.add(part, [pid])
-            else:
-                check(lib.ur_unpack_conv_weight_grad(dwp.data_ptr(), dwp.stride(0), g.data_ptr(), co, ci, cp, DT[dwp.dtype], _stream()),
-                      "ur_unpack_conv_weight_grad")
-            res.append(g)
+        _release(bw.weight_rot, ctx.rot_keys)
+        res = [None if dwp is None else _unpack_conv_grad(dwp, geom, pid) for dwp, geom, pid in zip(grads, ctx.geoms, ctx.pids)]
         bw.wgrad_stats["matrices"] += sum(r is not None for r in res)
         return (None, None, *res)
 
 
-packed_conv: dict = {}  # (id(fp32 conv weight), cin_pad) -> its PackConvWeights output for the current network forward (train_step)
-
-
 def pack_conv_weight(weight: torch.Tensor, dtype, cin_pad=None) -> torch.Tensor:
-    """differentiable version of layers.pack_conv3x3: [Co, Ci, 3, 3] fp32 master -> [Co][(ky,kx,ci_pad)] compute dtype."""
-    if packed_conv:
-        hit = packed_conv.get((id(weight), cin_pad))
-        if hit is not None and hit.dtype == dtype:
-            return hit
+    """differentiable version of layers.pack_conv3x3: [Co, Ci, 3, 3] fp32 master -> [Co][(ky,kx,ci_pad)] compute dtype: the
+    staged copy inside a network's stage, else a node of its own (PackConvWeight) or, off the GPU path, torch's repack."""
+    hit = PS.active.packed.get((id(weight), cin_pad)) if PS.active is not None else None
+    if hit is not None and hit.dtype == dtype:
+        return hit
     if weight.is_cuda and weight.dtype == torch.float32 and dtype in DT and weight.dim() == 4 and tuple(weight.shape[2:]) == (3, 3):
         return PackConvWeight.apply(weight, dtype, cin_pad)
     co, ci = weight.shape[:2]
@@ -500,38 +487,28 @@ def pack_conv_weight(weight: torch.Tensor, dtype, cin_pad=None) -> torch.Tensor:
         w = torch.nn.functional.pad(w, (0, cin_pad - ci))
     return w.reshape(co, -1).contiguous()
 
+
 class CastParams(Function):
     """fp32 master parameters -> compute dtype for MANY tensors per launch (``ur_cast_multi``: 128 tensors each; torch's
     ``_foreach_copy_`` takes its per-tensor path for mixed dtypes), and their gradients back to fp32 the same way when the
-    last of them has arrived.  Replaces one cast kernel per Linear
-    weight in each direction (~370 + ~330 launches per training step)."""
+    last of them has arrived.  Replaces one cast kernel per Linear weight in each direction (~370 + ~330 launches per step)."""
 
     @staticmethod
     def forward(ctx, dtype, *params):
-        import weakref
         ctx.set_materialize_grads(False)
         ctx.pids = [id(p) for p in params]
         outs = tuple(bw.cast_many([p.detach() for p in params], dtype, packed=True))
         ctx.wt_keys = []
         if outs and outs[0].is_cuda:
             flat = outs[0]._base if outs[0]._base is not None else outs[0]
-            _deferred_w[flat.untyped_storage().data_ptr()] = weakref.ref(flat)
-            bw.weight_t.sweep()  # entries of a forward that was never backpropagated, whose cast buffer is gone
-            if bw.BATCH_WT and bw.WGRAD:
-                # W^T for the dx GEMMs of the backward, 32 matrices per launch (bw.weight_t; dropped in the backward below)
-                w2 = [o.reshape(o.shape[0], -1) for o in outs if o.dim() >= 2]
-                w2 = [o for o in w2 if o.shape[0] % 8 == 0 and o.shape[1] % 8 == 0 and o.numel()]
-                for o, t in zip(w2, bw.transpose2d_many(w2) if w2 else []):
-                    key = (o.data_ptr(), tuple(o.shape))
-                    bw.weight_t.put(key, flat, t)  # valid while the flat cast buffer is alive
-                    ctx.wt_keys.append(key)
+            _defer_views_of(flat)
+            ctx.wt_keys = _derive_wt(outs, flat)
         return outs
 
     @staticmethod
     def backward(ctx, *grads):
         bw.wgrad_queue.flush()  # the weight gradients below may have been handed out uninitialised (Linear.backward)
-        for key in ctx.wt_keys:
-            bw.weight_t.pop(key, None)
+        _release(bw.weight_t, ctx.wt_keys)
         idx = [i for i, g in enumerate(grads) if g is not None]
         res = [None] * len(grads)
         bw.wgrad_stats["matrices"] += len(idx)
@@ -582,7 +559,6 @@ class LoraMerge(Function):
 
     @staticmethod
     def forward(ctx, dtype, scale, meta, *factors):
-        import weakref
         from . import lora
 
         ctx.set_materialize_grads(False)
@@ -605,16 +581,8 @@ class LoraMerge(Function):
             tables = _lora_cached("merge", rows, lambda rows=rows: lora.item_tables(rows, lora.multi_max()))
             lora.launch_merge_cast(tables, sdt, dtype)
         ctx.save_for_backward(*downs, *ups)
-        ctx.wt_keys = []
-        _deferred_w[flat.untyped_storage().data_ptr()] = weakref.ref(flat)
-        bw.weight_t.sweep()
-        if bw.BATCH_WT and bw.WGRAD:
-            w2 = [o.reshape(o.shape[0], -1) for o in outs]
-            w2 = [o for o in w2 if o.shape[0] % 8 == 0 and o.shape[1] % 8 == 0 and o.numel()]
-            for o, t in zip(w2, bw.transpose2d_many(w2) if w2 else []):
-                key = (o.data_ptr(), tuple(o.shape))
-                bw.weight_t.put(key, flat, t)  # valid while the flat buffer is alive
-                ctx.wt_keys.append(key)
+        _defer_views_of(flat)
+        ctx.wt_keys = _derive_wt(outs, flat)
         return tuple(outs)
 
     @staticmethod
@@ -622,8 +590,7 @@ class LoraMerge(Function):
         from . import lora
 
         bw.wgrad_queue.flush()  # the weight gradients below may have been handed out uninitialised (Linear.backward)
-        for key in ctx.wt_keys:
-            bw.weight_t.pop(key, None)
+        _release(bw.weight_t, ctx.wt_keys)
         saved = ctx.saved_tensors
         n = len(saved) // 2
         downs, ups = saved[:n], saved[n:]

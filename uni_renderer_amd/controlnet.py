@@ -114,7 +114,7 @@ class _DenoiserBase(ConfigModelMixin, nn.Module):
     def _autograd_mode(self, *tensors) -> bool:
         """True when this call must be differentiable: autograd is recording and a parameter or an input wants a
         gradient -- the situation of train/train.py:1324-1354 (modules called, then ``accelerator.backward(loss)``).
-        The forwards then run over ``autograd_ops`` (train_step.py: HIP forward AND backward kernels, same return
+        The forwards then run over ``autograd_ops`` (autograd_net.py: HIP forward AND backward kernels, same return
         tuples); under ``torch.no_grad()`` or with frozen parameters and no input that requires a gradient they take the
         fused inference path.  ``train()`` / ``eval()`` does not enter the decision (as in torch)."""
         if not torch.is_grad_enabled():
@@ -398,8 +398,8 @@ class UNet2DConditionModel(UNetIPAdapterMixin, UNetLoraMixin, _DenoiserBase):
         return self.forward_up(state, down_block_additional_residuals, mid_block_additional_residual, return_dict)
 
     def _forward_autograd(self, sample, timestep, ehs, down_res, mid_res, return_dict, lora_scale=None):
-        """The differentiable forward (train_step.unet_forward) behind the reference's signature and return tuple."""
-        from . import train_step as TS
+        """The differentiable forward (autograd_net.unet_forward) behind the reference's signature and return tuple."""
+        from . import autograd_net as TS
 
         if freeu_enabled(self):
             raise NotImplementedError(TS.FREEU_AUTOGRAD_MSG)
@@ -566,7 +566,7 @@ class AttributeEncoderModel(_DenoiserBase):
         scale_of(cross_attention_kwargs)  # a LoRA scale is accepted and ignored: this network has no adapters
         B = controlnet_cond.shape[0]
         if self._autograd_mode(controlnet_cond, encoder_hidden_states):
-            from . import train_step as TS
+            from . import autograd_net as TS
 
             dt = _compute_dtype(self.dtype, self.compute_dtype)
             res, mid, raw_down, raw_mid = TS.encoder_forward(
@@ -715,7 +715,7 @@ class AttributeDecoderModel(_DenoiserBase):
         B = sample.shape[0]
         if self._autograd_mode(sample, encoder_hidden_states, down_block_res_samples, down_block_additional_residuals,
                                up_block_additional_residuals, mid_block_additional_residual):
-            from . import train_step as TS
+            from . import autograd_net as TS
 
             dt = _compute_dtype(self.dtype, self.compute_dtype)
             g = lambda t: TS.to_nhwc_grad(t, dt)
@@ -773,7 +773,7 @@ class ControlNetModel(_DenoiserBase):
     ``conv_in(sample) + controlnet_cond_embedding(controlnet_cond)``.  ``forward(..., return_dict=False)`` returns
     ``(down_block_res_samples list[12], mid_block_res_sample)`` (ref 3260-3261), which go into
     ``UNet2DConditionModel.forward`` as ``down_block_additional_residuals`` / ``mid_block_additional_residual``.
-    With autograd recording and GPU tensors the forward is differentiable in every parameter (train_step.controlnet_forward);
+    With autograd recording and GPU tensors the forward is differentiable in every parameter (autograd_net.controlnet_forward);
     CPU tensors raise ``CONTROLNET_AUTOGRAD_MSG``, an image that requires a gradient raises ``layers.COND_IMAGE_GRAD_MSG``."""
 
     @register_to_config
@@ -885,7 +885,7 @@ class ControlNetModel(_DenoiserBase):
                          added_cond_kwargs=added_cond_kwargs)
         scale_of(cross_attention_kwargs)  # a LoRA scale is accepted and ignored: this network has no adapters
         if self._autograd_mode(sample, controlnet_cond, encoder_hidden_states):
-            # training (train_step.controlnet_forward: HIP forward AND backward kernels).  There is no differentiable path off
+            # training (autograd_net.controlnet_forward: HIP forward AND backward kernels).  There is no differentiable path off
             # the GPU, and none into the image.  Not covered: GraphedTrainStep, parallel.GradientBuckets / GradSink and LoRA
             # for this network.
             if not (sample.is_cuda and controlnet_cond.is_cuda and next(self.parameters()).is_cuda):
@@ -893,7 +893,7 @@ class ControlNetModel(_DenoiserBase):
             if controlnet_cond.requires_grad:
                 from .layers import COND_IMAGE_GRAD_MSG
                 raise NotImplementedError(COND_IMAGE_GRAD_MSG)
-            from . import train_step as TS
+            from . import autograd_net as TS
 
             dt = _compute_dtype(self.dtype, self.compute_dtype)
             res, mid = TS.controlnet_forward(

@@ -541,7 +541,7 @@ class UNetLoraMixin:
         merged into the parameter, else the parameter -- and ``s`` the scale in force.  Raises when the set-up cannot train."""
         st = self._lora
         if st.trainable is None:
-            from .train_step import LORA_AUTOGRAD_MSG
+            from .autograd_net import LORA_AUTOGRAD_MSG
 
             raise NotImplementedError(LORA_AUTOGRAD_MSG)
         if st.active != [st.trainable]:

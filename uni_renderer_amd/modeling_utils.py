@@ -154,7 +154,7 @@ class ConfigModelMixin:
         controlnet.py:745-747 / 1653-1655 / 2338-2340: every sub-block that HAS a ``gradient_checkpointing`` attribute gets it
         set; unet_2d_blocks.py:1172-1197: in training mode a checkpointed block runs each of its ResnetBlock2D under
         ``torch.utils.checkpoint.checkpoint(..., use_reentrant=False)``, its attention is not checkpointed).  The training
-        forward (train_step._down_mid / _up_out) honours the flag: the resnet's activations (two GroupNorm outputs, the conv1
+        forward (autograd_net._down_mid / _up_out) honours the flag: the resnet's activations (two GroupNorm outputs, the conv1
         output) are dropped after the forward and recomputed by the same HIP kernels in the backward -- bit-identical
         gradients (tests/test_train_gpu.py).  Not needed for memory here (cfg 4's per-GPU step peaks at ~38 GB of 288 GB)."""
         self._set_gc(True)

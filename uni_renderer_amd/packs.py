@@ -4,7 +4,7 @@ A ``Recipe`` says, for one kind of module, which tensors a packed operand is mad
 layout primitives of layers.py and tchain.py).  ``one`` caches it for the module path (layers.py, controlnet.py, vae.py),
 ``stacked`` caches it stacked over the streams for the grouped path (fused.py, hoist.py).  A cached value is valid for the
 ``(data_ptr, _version, device)`` of exactly the tensors ``params`` names; tests/test_packs_cpu.py checks per recipe that those
-are the tensors ``build`` reads.  The training path keeps its own differentiable copies (train_step.py, autograd_ops.py).
+are the tensors ``build`` reads.  The training path keeps its own differentiable copies (param_stage.py, autograd_ops.py).
 """
 from __future__ import annotations
 
